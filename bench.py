@@ -3,13 +3,16 @@
 (forward + loss + backward + clip_grad_norm_(12) + SGD-Nesterov step) on synthetic device-resident batches,
 dummyLoad style (reference: nnUNet_variants/benchmarking/nnUNetTrainerV2_dummyLoad.py:26-64).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 Workload (every N): BASELINE.json configs[1] = Task009_Spleen Generic_UNet, bs=2 per GPU, patch 48x192x192, fp32, softmax
 Dice+CE with deep supervision.  N > 1: one rank per GPU over RCCL (weak scaling; gradients all-reduced (mean) overlapped with
 backward on a side stream) — launched by torch.distributed.run; when called as plain `python bench.py --gpus N` the script
 re-executes itself under torch.distributed.run with N ranks.  --workload task100 | resenc | infer select BASELINE configs[2..4],
 --patch 96 192 192 the plans' native patch, --precision bf16 the mixed-precision mode of configs[3].
-Prints ONE JSON line on rank 0 (N = 1: with `roofline` of the dominant kernel and `cpu_baseline`).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline line; --full adds what
+else the benchmark measures and checks: `roofline` of the dominant kernel (N = 1: with two rocprofv3 traffic passes), `cpu_baseline`,
+the other BASELINE configs under `also` (default workload) and, at N > 1, the cross-rank checks and the early headline lines.
+--dump-outputs DIR writes what the timed path computed in its last step to DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import csv
@@ -54,6 +57,29 @@ def executed_fraction(kernel):
         if kernel.startswith(prefix):
             return f
     return 1.0
+
+
+DUMP_CAP = 7 << 20      # elements per dumped array (28 MiB of float32): two such arrays and the loss values stay below 64 MB
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: DIR/<name>.npy for every output of the timed path's last step, float64 for the loss values and float32
+    for everything else.  An array of at most DUMP_CAP elements is written whole, in its shape; a larger one as a fixed sample of
+    DUMP_CAP of its elements in a 1-D array (flat indices drawn with seed 0, sorted: the same sample in every run of the same shape)."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            flat = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_CAP))
+            t = t[tuple(torch.from_numpy(i).to(t.device) for i in np.unravel_index(flat, tuple(t.shape)))]
+        np.save(os.path.join(d, name + '.npy'), t.to(torch.float64 if name == 'loss' else torch.float32).cpu().numpy())
+
+
+def training_outputs(r):
+    """What a caller of the training step holds after its last call: the loss value(s) it returned, the full-resolution logits of
+    that step's forward and the flat parameter buffer after its SGD update."""
+    res = r['res'] if isinstance(r['res'], (tuple, list)) else (r['res'],)
+    return {'loss': torch.cat([t.detach().double().reshape(-1) for t in res]), 'logits': r['step'].last_logits, 'params': r['step'].eng.flat}
 
 
 def build_network(workload):
@@ -417,6 +443,8 @@ def bench_infer(args, dev, rank, world, ddp, emit=True):
     mk = lambda mode: (lambda v=vol: predict_3D(net, v, bool(args.mirror), (0, 1, 2), True, 0.5, patch, None, True, 'constant', None, True,
                                                 False, mixed, tile_shard=shard, return_device_tensors=mode))
 
+    last = {}
+
     def timed(fn):
         for _ in range(max(1, min(args.warmup, 1))):
             fn()
@@ -425,7 +453,7 @@ def bench_infer(args, dev, rank, world, ddp, emit=True):
             dist.barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            fn()
+            last['out'] = fn()
         torch.cuda.synchronize()
         if ddp:
             dist.barrier()
@@ -435,13 +463,23 @@ def bench_infer(args, dev, rank, world, ddp, emit=True):
             all_reduce_dev(tmax, dist.ReduceOp.MAX)
             dt = float(tmax.item())
         return dt
+
+    def dump_last():
+        # the headline pass's last volume, written before a later pass reuses the buffers its probabilities alias
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'segmentation': last['out'][0], 'probabilities': last['out'][1]})
+        last.clear()
     run = mk(True)
-    dt_sharded = timed(run)             # result left sharded on the devices (slab per rank)
     variants, check = None, None
     if world > 1:
+        dt_sharded = timed(run) if args.full else None      # result left sharded on the devices (slab per rank)
         # the reference returns a WHOLE (seg, probabilities) per case (predict_MultiTalent.py:222-266): the gathered variant ends with the
         # whole mask on every rank (one uint8 all_gather: 134 MB at 512^3; the 25 GB of probabilities stay sharded) — that is `value`
         dt = timed(mk('mask'))
+    else:
+        dt = timed(run)
+    dump_last()
+    if world > 1 and args.full:
         variants = {"sharded_volumes_per_min": round(60.0 * args.steps / dt_sharded, 3), "mask_gathered_volumes_per_min": round(60.0 * args.steps / dt, 3),
                     "value_is": "mask_gathered"}
         # correctness inside the run: tile-sharded == unsharded on a smaller volume (own slab of the probabilities, whole gathered mask)
@@ -464,8 +502,6 @@ def bench_infer(args, dev, rank, world, ddp, emit=True):
         net._sliding_window_cache = None
         del seg1, p1, segf, pslab
         torch.cuda.empty_cache()
-    else:
-        dt = dt_sharded
     groups = None
     if not args.no_roofline:          # every rank repeats one volume with per-launch events (the sharded run exchanges slabs)
         with ConvTimer() as t:
@@ -548,8 +584,9 @@ def all_reduce_dev(t, op):
     return t
 
 
-def time_training(workload, precision, patch, B, steps, warmup, dev, rank, world, ddp):
-    """W untimed + K timed training iterations of `workload`, bracketed by barrier + synchronize, max over ranks."""
+def time_training(workload, precision, patch, B, steps, warmup, dev, rank, world, ddp, check_ranks=True):
+    """W untimed + K timed training iterations of `workload`, bracketed by barrier + synchronize, max over ranks.  check_ranks (N > 1):
+    the parameter checksum over the ranks after the timed steps."""
     from multitalent_amd.training.hot_loop import FusedTrainStep
     torch.manual_seed(1234)           # identical initial weights on all ranks (DDP broadcast semantics)
     net = build_network(workload)
@@ -582,7 +619,7 @@ def time_training(workload, precision, patch, B, steps, warmup, dev, rank, world
         rank_ms = {'max': round(float(tmax[1]) / steps * 1e3, 3), 'min': round(-float(tmax[2]) / steps * 1e3, 3)}
     loss = res[0] if isinstance(res, tuple) else res
     comm = step.reducer.stats() if step.reducer is not None else None
-    if ddp:
+    if ddp and check_ranks:
         # the ranks must hold bit-identical parameters after the timed steps (same initial weights, all-reduced gradients, the same
         # optimizer arithmetic): a checksum of the flat parameter buffer, max - min over the ranks, must be exactly 0
         flat = step.eng.flat
@@ -594,9 +631,11 @@ def time_training(workload, precision, patch, B, steps, warmup, dev, rank, world
         comm = dict(comm or {})
         comm['param_checksum_spread_over_ranks'] = spread
         comm['params_identical_on_all_ranks'] = spread == 0.0
+    if ddp:
+        comm = dict(comm or {})
         comm['loss_finite'] = bool(np.isfinite(float(loss)))
         comm['ms_per_step_over_ranks_before_barrier'] = rank_ms
-    return {'dt': dt, 'ms': dt / steps * 1e3, 'value': world * B * steps / dt, 'loss': float(loss), 'step': step, 'x': x, 'largs': largs,
+    return {'dt': dt, 'ms': dt / steps * 1e3, 'value': world * B * steps / dt, 'loss': float(loss), 'res': res, 'step': step, 'x': x, 'largs': largs,
             'net': net, 'comm': comm}
 
 
@@ -677,6 +716,7 @@ def measure_also(args, dev, rank, world, ddp):
     def infer_entry():
         ia = argparse.Namespace(**vars(args))
         ia.workload, ia.mirror, ia.steps, ia.warmup, ia.no_cpu_baseline, ia.no_traffic, ia.precision = 'infer', 0, 2, 1, True, True, 'fp32'
+        ia.dump_outputs = None
         e = bench_infer(ia, dev, rank, world, ddp, emit=False)
         return None if e is None else {k: e[k] for k in ("metric", "value", "unit", "ms_per_step", "dtype", "config", "roofline", "scaling", "comm",
                                                          "variants", "sharded_equals_unsharded") if k in e}
@@ -687,6 +727,7 @@ def measure_also(args, dev, rank, world, ddp):
         ia = argparse.Namespace(**vars(args))
         ia.workload, ia.mirror, ia.steps, ia.warmup, ia.no_cpu_baseline, ia.no_traffic, ia.no_roofline, ia.precision = 'infer', 1, 1, 1, True, True, True, 'fp32'
         ia.volume = [128, 384, 384]
+        ia.dump_outputs = None
 
         def tta_entry():
             e = bench_infer(ia, dev, rank, world, ddp, emit=False)
@@ -720,7 +761,14 @@ def main():
     ap.add_argument('--no-also', action='store_true', help='headline workload only (default run: + the other BASELINE configs under "also")')
     ap.add_argument('--also-steps', type=int, default=5)
     ap.add_argument('--no-traffic', action='store_true', help='skip the two rocprofv3 --pmc child passes (roofline.traffic = null)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: roofline (+ traffic), cpu_baseline, also, the N > 1 cross-rank checks and early lines; '
+                         'the --no-* switches trim it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, < 64 MB)')
     args = ap.parse_args()
+    if not args.full:        # a plain run: set up, warm up, time the steps, dump, print the headline line — nothing else
+        args.no_cpu_baseline = args.no_roofline = args.no_also = args.no_traffic = True
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         respawn_under_torchrun(args.gpus)
@@ -745,11 +793,13 @@ def main():
         return bench_infer(args, dev, rank, world, ddp)
     patch = tuple(args.patch)
     B = args.batch or DEFAULT_BATCH[workload]
-    r = time_training(workload, args.precision, patch, B, args.steps, args.warmup, dev, rank, world, ddp)
+    r = time_training(workload, args.precision, patch, B, args.steps, args.warmup, dev, rank, world, ddp, check_ranks=args.full)
+    if args.dump_outputs and rank == 0:           # before the roofline pass runs more steps
+        dump_outputs(args.dump_outputs, training_outputs(r))
     line = None
     if rank == 0:
         line = training_line(r, workload, args.precision, patch, B, args.steps, args.warmup, world)
-    if ddp:
+    if ddp and args.full:
         # N > 1: the headline leaves the process as soon as it is measured — BEFORE the per-launch roofline pass (every rank, collectives
         # inside) and before the other configs (first RCCL contact of the sharded sliding window and of two more networks): a hang or a
         # crash in either must not cost the headline.  The complete line follows as the LAST line of the job with the same headline fields.

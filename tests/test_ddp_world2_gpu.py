@@ -299,7 +299,7 @@ def test_bench_two_ranks_self_validation_on_one_gpu(extra):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-also', '--no-roofline'] + extra,
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-also', '--no-roofline'] + extra,
                          capture_output=True, text=True, timeout=1200, env=dict(_launcher_free_env(), MT_BENCH_ONE_GPU='1'))
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
@@ -322,7 +322,7 @@ def test_bench_eight_ranks_on_one_gpu(extra):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--no-also', '--no-roofline'] + extra,
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--gpus', '8', '--steps', '2', '--warmup', '1', '--no-also', '--no-roofline'] + extra,
                          capture_output=True, text=True, timeout=1800, env=dict(_launcher_free_env(), MT_BENCH_ONE_GPU='1'))
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
@@ -342,7 +342,7 @@ def test_bench_headline_survives_a_failing_also_leg():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-roofline'],
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-roofline'],
                          capture_output=True, text=True, timeout=1200,
                          env=dict(_launcher_free_env(), MT_BENCH_ONE_GPU='1', MT_BENCH_INJECT_ALSO_FAILURE='all'))
     assert out.returncode == 0, out.stderr[-3000:]
@@ -365,7 +365,7 @@ def test_bench_two_ranks_smoke(extra):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-also'] + extra,
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-also'] + extra,
                          capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0'))
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])

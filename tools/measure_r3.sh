@@ -1,15 +1,15 @@
 # every bench line quoted in DESIGN.md / README.md for round 3, one MI355X: gpurun_out/meas_r3/*.json (copied to profiles/r03_*.json),
 # rocprofv3 kernel statistics of the same commands and the SQ counters of the dominant kernel
 O=gpurun_out/meas_r3; mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/default.err
-python bench.py --workload task100 --steps 8 --warmup 2 --no-also > $O/bench_task100_fp32.json 2> $O/task100.err
-python bench.py --workload resenc --steps 8 --warmup 2 --no-also > $O/bench_resenc_fp32.json 2> $O/resenc.err
-python bench.py --workload resenc --precision bf16 --steps 8 --warmup 2 --no-cpu-baseline --no-also > $O/bench_resenc_bf16.json 2>> $O/resenc.err
-python bench.py --precision bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-also > $O/bench_task009_bf16.json 2>> $O/default.err
-python bench.py --workload task100 --precision bf16 --steps 8 --warmup 2 --no-cpu-baseline --no-also > $O/bench_task100_bf16.json 2>> $O/task100.err
-python bench.py --workload infer --mirror 0 --steps 2 --warmup 1 --no-also > $O/bench_infer_nomirror_fp32.json 2> $O/infer.err
-python bench.py --workload infer --mirror 1 --steps 1 --warmup 1 --no-traffic --no-cpu-baseline --no-also > $O/bench_infer_mirror_fp32.json 2>> $O/infer.err
-python bench.py --workload infer --mirror 0 --precision bf16 --steps 2 --warmup 1 --no-cpu-baseline --no-traffic --no-also > $O/bench_infer_nomirror_bf16.json 2>> $O/infer.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/default.err
+python bench.py --full --workload task100 --steps 8 --warmup 2 --no-also > $O/bench_task100_fp32.json 2> $O/task100.err
+python bench.py --full --workload resenc --steps 8 --warmup 2 --no-also > $O/bench_resenc_fp32.json 2> $O/resenc.err
+python bench.py --full --workload resenc --precision bf16 --steps 8 --warmup 2 --no-cpu-baseline --no-also > $O/bench_resenc_bf16.json 2>> $O/resenc.err
+python bench.py --full --precision bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-also > $O/bench_task009_bf16.json 2>> $O/default.err
+python bench.py --full --workload task100 --precision bf16 --steps 8 --warmup 2 --no-cpu-baseline --no-also > $O/bench_task100_bf16.json 2>> $O/task100.err
+python bench.py --full --workload infer --mirror 0 --steps 2 --warmup 1 --no-also > $O/bench_infer_nomirror_fp32.json 2> $O/infer.err
+python bench.py --full --workload infer --mirror 1 --steps 1 --warmup 1 --no-traffic --no-cpu-baseline --no-also > $O/bench_infer_mirror_fp32.json 2>> $O/infer.err
+python bench.py --full --workload infer --mirror 0 --precision bf16 --steps 2 --warmup 1 --no-cpu-baseline --no-traffic --no-also > $O/bench_infer_nomirror_bf16.json 2>> $O/infer.err
 bash tools/profile_r3.sh task009_fp32 task009_fp32_overlap task100_fp32 resenc_bf16 infer_nomirror_fp32 > $O/profile.log 2>&1
 cp gpurun_out/prof_r3/*_kernel_stats.csv $O/ 2>/dev/null
 # SQ counters of the dominant kernel (two passes of <= 8 counters; no other trace domain)

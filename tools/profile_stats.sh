@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_${ROUND:-r6}
 mkdir -p $O
 run() {  # tag, bench args...
   tag=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/$tag -o b -- python $R/bench.py "$@" --no-cpu-baseline --no-traffic --no-also > $O/${tag}_profiled.json 2> $O/${tag}.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/$tag -o b -- python $R/bench.py --full "$@" --no-cpu-baseline --no-traffic --no-also > $O/${tag}_profiled.json 2> $O/${tag}.err
   f=$(find $O/$tag -name '*kernel_stats.csv' | head -1)
   [ -n "$f" ] && cp $f $O/${tag}_kernel_stats.csv
   rm -rf $O/$tag
