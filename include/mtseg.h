@@ -417,6 +417,25 @@ int mt_affine_sample(const float* src, int N, int C, int D, int H, int W, float*
 int mt_resample_classify(const float* probs, int C, int D, int H, int W, int OD, int OH, int OW, int sep_axis,
                          const int32_t* class_order, int use_regions, uint8_t* out, long FD, long FH, long FW,
                          int bD, int bH, int bW, mt_stream_t stream);
+/* Connected-component post-processing (remove_all_but_the_largest_connected_component, postprocessing/connected_components.py:48-101).
+ * mt_cc_label3d: `lmap, num_objects = scipy.ndimage.label(mask)` (:76) with scipy's default 3-D structure, 6-connectivity (face
+ * neighbours only), on the mask {v : member[seg[v]] != 0} of a contiguous uint8 volume seg[D, H, W].  member: HOST array of 256
+ * entries (a tuple entry such as (1, 2) of for_which_classes is one joint mask).  Outputs, caller-allocated device arrays of
+ * V = D*H*W int32:
+ *   labels[v] = the smallest linear index (d*H + h)*W + w of v's component, -1 for background — a function of the partition alone,
+ *               bit-identical from run to run whatever the scheduling;
+ *   sizes[v]  = the component's exact voxel count where v is that smallest index (labels[v] == v), 0 everywhere else;
+ *   stats[0]  = number of components, stats[1] = largest count (0 when the mask is empty); device int32[2].
+ * mt_cc_remove: the removal loop (:85-100) in place on seg, for the labelling above: a component with count c is zeroed when
+ *   (double)c * volume_per_voxel != (double)stats[1] * volume_per_voxel   (every component tied for the largest is kept, `!= maximum_size`)
+ * and, when use_min_size != 0, (double)c * volume_per_voxel < min_size — evaluated in fp64 on the device, the same IEEE product as the
+ * reference's np.int64 * float.  *removed (device int32) = the largest removed count, 0 when nothing was removed; the host forms
+ * largest_removed = removed * volume_per_voxel and kept_size = stats[1] * volume_per_voxel as the reference does.
+ * Both reject V > INT32_MAX with MT_EINVAL before any launch. */
+int mt_cc_label3d(const uint8_t* seg, int D, int H, int W, const uint8_t* member, int32_t* labels, int32_t* sizes, int32_t* stats,
+                  mt_stream_t stream);
+int mt_cc_remove(uint8_t* seg, int D, int H, int W, const int32_t* labels, const int32_t* sizes, const int32_t* stats,
+                 double volume_per_voxel, int use_min_size, double min_size, int32_t* removed, mt_stream_t stream);
 /* ---- device-side target preparation ----------------------------------------
  * Deep-supervision label pyramid: DownsampleSegForDSTransform2 / downsample_seg_for_ds_transform2 (downsampling.py:70-104,
  * order 0 = nearest through batchgenerators' resize_segmentation -> skimage.transform.resize(order 0, mode "edge") ->

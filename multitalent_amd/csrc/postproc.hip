@@ -1,0 +1,301 @@
+// Connected-component post-processing on the device: "keep only the largest connected component" of
+// postprocessing/connected_components.py:48-101 (scipy.ndimage.label with its default 3-D structure = 6-connectivity, :76,
+// then the removal loop :85-100).  Union-find labelling in four launches:
+//   1. cc_local_kernel   one 8x16x16 brick per 256-thread workgroup: union-find in LDS (atomicMin links the larger root under
+//                        the smaller), labels[v] = global linear index of the brick-local root, sizes[brick-local root] = voxel
+//                        count of the brick-local piece, every other sizes[] entry 0;
+//   2. cc_merge_kernel   the low faces of every brick against the neighbouring brick: union in global memory (atomicMin);
+//   3. cc_flatten_kernel labels[v] = final root = the smallest linear index of the component; roots are counted;
+//   4. cc_count_kernel   every non-final brick-local root adds its piece count to its final root (one atomic per
+//                        (brick, component) pair, not per voxel) and clears its own entry.
+// cc_remove_kernel then zeroes, in place, the voxels of the components that are not kept.
+#include "mt_common.h"
+
+#define CC_BD 8
+#define CC_BH 16
+#define CC_BW 16
+#define CC_BV (CC_BD * CC_BH * CC_BW)   // 2048 voxels per brick, 8 per thread
+#define CC_THREADS 256
+
+struct CCMember { uint32_t bits[8]; };   // 256-bit membership of the uint8 labels
+
+__device__ __forceinline__ bool cc_member(const CCMember& m, uint8_t v) { return (m.bits[v >> 5] >> (v & 31)) & 1u; }
+
+// ---- LDS union-find (one workgroup) ----------------------------------------------------------------------------------------
+__device__ __forceinline__ int cc_lds_load(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ int cc_lfind(int* par, int x) {
+  int p;
+  while ((p = cc_lds_load(par + x)) != x) x = p;
+  return x;
+}
+// Links the larger root under the smaller.  If the atomicMin finds `a` already linked (old != a), par[a] now holds min(old, b)
+// and the pair (old, b) is united in the next turn: no equivalence is lost, and a parent pointer only ever decreases.
+__device__ __forceinline__ void cc_lunion(int* par, int a, int b) {
+  while (true) {
+    a = cc_lfind(par, a);
+    b = cc_lfind(par, b);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = atomicMin(par + a, b);
+    if (old == a) return;
+    a = old;
+  }
+}
+
+// ---- global union-find (merge launch) -------------------------------------------------------------------------------------
+// Parent pointers are read with agent-scope atomic loads: another workgroup's link may have been made on another XCD within
+// this launch, and a plain load could return a line this CU's L1 or this XCD's L2 still holds.
+__device__ __forceinline__ int cc_gload(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int cc_gfind(int* L, int x) {
+  int p;
+  while ((p = cc_gload(L + x)) != x) x = p;
+  return x;
+}
+__device__ __forceinline__ void cc_gunion(int* L, int a, int b) {
+  while (true) {
+    a = cc_gfind(L, a);
+    b = cc_gfind(L, b);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (old == a) return;
+    a = old;
+  }
+}
+
+struct CCGeom { int D, H, W, nbh, nbw; };
+
+__device__ __forceinline__ void cc_brick_origin(const CCGeom& g, int b, int& d0, int& h0, int& w0) {
+  const int bw = b % g.nbw, bh = (b / g.nbw) % g.nbh, bd = b / (g.nbw * g.nbh);
+  d0 = bd * CC_BD; h0 = bh * CC_BH; w0 = bw * CC_BW;
+}
+
+__global__ __launch_bounds__(CC_THREADS) void cc_local_kernel(const uint8_t* __restrict__ seg, const CCMember m, const CCGeom g,
+                                                              int nb, int32_t* __restrict__ L, int32_t* __restrict__ S,
+                                                              int32_t* __restrict__ stats) {
+  __shared__ int par[CC_BV];
+  __shared__ int cnt[CC_BV];
+  if (blockIdx.x == 0 && threadIdx.x < 2) stats[threadIdx.x] = 0;
+  const int t = threadIdx.x, lh = t >> 4, lw = t & 15;
+  for (int b = blockIdx.x; b < nb; b += gridDim.x) {
+    int d0, h0, w0;
+    cc_brick_origin(g, b, d0, h0, w0);
+    const int h = h0 + lh, w = w0 + lw;
+    const bool hw_in = h < g.H && w < g.W;
+    unsigned fg = 0;                                 // bit ld: this thread's voxel of slice ld is in the mask
+#pragma unroll
+    for (int ld = 0; ld < CC_BD; ++ld) {
+      const int d = d0 + ld, i = ld * (CC_BH * CC_BW) + t;
+      bool f = false;
+      if (hw_in && d < g.D) f = cc_member(m, seg[((size_t)d * g.H + h) * g.W + w]);
+      fg |= (unsigned)f << ld;
+      par[i] = f ? i : -1;
+      cnt[i] = 0;
+    }
+    __syncthreads();
+    // a neighbour's entry is >= 0 exactly when it is in the mask, whatever links other threads are making meanwhile
+#pragma unroll
+    for (int ld = 0; ld < CC_BD; ++ld) {
+      if (!((fg >> ld) & 1)) continue;
+      const int i = ld * (CC_BH * CC_BW) + t;
+      if (lw > 0 && cc_lds_load(par + i - 1) >= 0) cc_lunion(par, i, i - 1);
+      if (lh > 0 && cc_lds_load(par + i - CC_BW) >= 0) cc_lunion(par, i, i - CC_BW);
+      if (ld > 0 && ((fg >> (ld - 1)) & 1)) cc_lunion(par, i, i - CC_BH * CC_BW);
+    }
+    __syncthreads();
+    int root[CC_BD];
+#pragma unroll
+    for (int ld = 0; ld < CC_BD; ++ld) {
+      const int i = ld * (CC_BH * CC_BW) + t;
+      const bool f = (fg >> ld) & 1;
+      root[ld] = f ? cc_lfind(par, i) : -1;
+      // per-wave aggregation of the piece counts: one LDS atomic per distinct root of the wave, not one per voxel
+      uint64_t active = __ballot(f);
+      while (active) {
+        const int leader = __ffsll((unsigned long long)active) - 1;
+        const int rl = __shfl(root[ld], leader, 64);
+        const uint64_t same = __ballot(f && root[ld] == rl);
+        if ((int)(threadIdx.x & 63) == leader) atomicAdd(cnt + rl, __popcll(same));
+        active &= ~same;
+      }
+    }
+    __syncthreads();
+    if (hw_in) {
+#pragma unroll
+      for (int ld = 0; ld < CC_BD; ++ld) {
+        const int d = d0 + ld;
+        if (d >= g.D) break;
+        const int i = ld * (CC_BH * CC_BW) + t;
+        const size_t v = ((size_t)d * g.H + h) * g.W + w;
+        int lab = -1;
+        if (root[ld] >= 0) {
+          const int r = root[ld];
+          // local index order (ld, lh, lw) is the linear order inside the brick: the local root is the piece's smallest index
+          lab = (int)(((size_t)(d0 + (r >> 8)) * g.H + (h0 + ((r >> 4) & 15))) * g.W + (w0 + (r & 15)));
+        }
+        L[v] = lab;
+        S[v] = (root[ld] == i) ? cnt[i] : 0;
+      }
+    }
+    __syncthreads();                                 // LDS is reused by the next brick
+  }
+}
+
+// Faces d = d0, h = h0, w = w0 of every brick against the voxel before it.  Threads 0..255: the D face (one (h, w) each);
+// threads 0..127 also the H face (ld, lw), threads 128..255 the W face (ld, lh).
+__global__ __launch_bounds__(CC_THREADS) void cc_merge_kernel(const CCGeom g, int nb, int32_t* __restrict__ L) {
+  const int t = threadIdx.x;
+  const size_t HW = (size_t)g.H * g.W;
+  for (int blk = blockIdx.x; blk < nb; blk += gridDim.x) {
+    int d0, h0, w0;
+    cc_brick_origin(g, blk, d0, h0, w0);
+    if (d0 > 0) {
+      const int h = h0 + (t >> 4), w = w0 + (t & 15);
+      if (h < g.H && w < g.W) {
+        const size_t v = ((size_t)d0 * g.H + h) * g.W + w;
+        const int a = L[v], b = L[v - HW];     // >= 0 <=> in the mask: fixed since the previous launch
+        if (a >= 0 && b >= 0) cc_gunion(L, a, b);
+      }
+    }
+    if (t < 128) {
+      const int d = d0 + (t >> 4), w = w0 + (t & 15);
+      if (h0 > 0 && d < g.D && w < g.W) {
+        const size_t v = ((size_t)d * g.H + h0) * g.W + w;
+        const int a = L[v], b = L[v - g.W];
+        if (a >= 0 && b >= 0) cc_gunion(L, a, b);
+      }
+    } else {
+      const int d = d0 + ((t - 128) >> 4), h = h0 + ((t - 128) & 15);
+      if (w0 > 0 && d < g.D && h < g.H) {
+        const size_t v = ((size_t)d * g.H + h) * g.W + w0;
+        const int a = L[v], b = L[v - 1];
+        if (a >= 0 && b >= 0) cc_gunion(L, a, b);
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ int cc_block_sum(int v, int* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+__device__ __forceinline__ int cc_block_max(int v, int* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return max(max(red[0], red[1]), max(red[2], red[3]));
+}
+
+// labels[v] = root.  Plain loads suffice here: the links are final since the merge launch, and a value another thread of
+// THIS launch stores (a final root) is an ancestor of what was there before, so any mix of old and new values walks to the
+// same root.
+__global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(int32_t* __restrict__ L, long V, int32_t* __restrict__ stats) {
+  __shared__ int red[4];
+  int nroots = 0;
+  for (long v = (long)blockIdx.x * CC_THREADS + threadIdx.x; v < V; v += (long)gridDim.x * CC_THREADS) {
+    int x = L[v];
+    if (x < 0) continue;
+    int p;
+    while ((p = L[x]) != x) x = p;
+    L[v] = x;
+    nroots += (x == (int)v);
+  }
+  const int n = cc_block_sum(nroots, red);
+  if (threadIdx.x == 0 && n) atomicAdd(stats, n);
+}
+
+// sizes[root] += piece count of every brick-local root that is not a final root; sizes[v] of such a v is read and cleared by
+// its own thread only (nothing adds to an entry that is not a final root).  The running totals returned by the atomics bound
+// each component's final count from below and reach it at the last add: their maximum is the largest component.
+__global__ __launch_bounds__(CC_THREADS) void cc_count_kernel(const int32_t* __restrict__ L, int32_t* __restrict__ S, long V,
+                                                              int32_t* __restrict__ stats) {
+  __shared__ int red[4];
+  int mx = 0;
+  for (long v = (long)blockIdx.x * CC_THREADS + threadIdx.x; v < V; v += (long)gridDim.x * CC_THREADS) {
+    const int c = S[v];
+    if (c <= 0) continue;
+    const int r = L[v];
+    if (r == (int)v) { mx = max(mx, c); continue; }
+    mx = max(mx, atomicAdd(S + r, c) + c);
+    S[v] = 0;
+  }
+  const int m = cc_block_max(mx, red);
+  if (threadIdx.x == 0 && m) atomicMax(stats + 1, m);
+}
+
+// Removal rule of connected_components.py:92-99: a component is removed when its size differs from the largest size (every
+// component tied for the largest is kept) and, with a minimum given, its size is below it.  Sizes are (double)count * vpv, the
+// same IEEE product as the reference's np.int64 * float.
+__global__ __launch_bounds__(CC_THREADS) void cc_remove_kernel(uint8_t* __restrict__ seg, const int32_t* __restrict__ L,
+                                                               const int32_t* __restrict__ S, long V,
+                                                               const int32_t* __restrict__ stats, double vpv, double min_size,
+                                                               int use_min, int32_t* __restrict__ removed) {
+  __shared__ int red[4];
+  const double max_size = (double)stats[1] * vpv;
+  int mx = 0;
+  for (long v = (long)blockIdx.x * CC_THREADS + threadIdx.x; v < V; v += (long)gridDim.x * CC_THREADS) {
+    const int r = L[v];
+    if (r < 0) continue;
+    const int c = S[r];
+    const double size = (double)c * vpv;
+    if (size != max_size && (!use_min || size < min_size)) {
+      seg[v] = 0;
+      mx = max(mx, c);
+    }
+  }
+  const int m = cc_block_max(mx, red);
+  if (threadIdx.x == 0 && m) atomicMax(removed, m);
+}
+
+static int cc_stream_blocks(long V) {
+  const int cap = mt_device_cus(mt_current_device()) * 8;
+  const int b = mt_cdiv(V, CC_THREADS);
+  return b < cap ? b : cap;
+}
+
+extern "C" int mt_cc_label3d(const uint8_t* seg, int D, int H, int W, const uint8_t* member, int32_t* labels, int32_t* sizes,
+                             int32_t* stats, mt_stream_t stream) {
+  MT_REQUIRE(seg && member && labels && sizes && stats, "cc_label3d: null pointer");
+  MT_REQUIRE(D > 0 && H > 0 && W > 0, "cc_label3d: bad shape %d x %d x %d", D, H, W);
+  const long V = (long)D * H * W;
+  MT_REQUIRE(V <= (long)INT32_MAX, "cc_label3d: %ld voxels exceed the int32 index range", V);
+  CCMember m;
+  for (int k = 0; k < 8; ++k) m.bits[k] = 0;
+  for (int k = 0; k < 256; ++k) if (member[k]) m.bits[k >> 5] |= 1u << (k & 31);
+  CCGeom g;
+  g.D = D; g.H = H; g.W = W; g.nbh = mt_cdiv(H, CC_BH); g.nbw = mt_cdiv(W, CC_BW);
+  const long nb = (long)mt_cdiv(D, CC_BD) * g.nbh * g.nbw;     // <= V: fits in int
+  const int grid = nb < (1L << 20) ? (int)nb : (1 << 20);          // bricks beyond the grid: block-stride loop
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(cc_local_kernel, dim3(grid), dim3(CC_THREADS), 0, s, seg, m, g, (int)nb, labels, sizes, stats);
+  MT_CHECK_LAUNCH("cc_label3d (local)");
+  hipLaunchKernelGGL(cc_merge_kernel, dim3(grid), dim3(CC_THREADS), 0, s, g, (int)nb, labels);
+  MT_CHECK_LAUNCH("cc_label3d (merge)");
+  const int blocks = cc_stream_blocks(V);
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(blocks), dim3(CC_THREADS), 0, s, labels, V, stats);
+  MT_CHECK_LAUNCH("cc_label3d (flatten)");
+  hipLaunchKernelGGL(cc_count_kernel, dim3(blocks), dim3(CC_THREADS), 0, s, labels, sizes, V, stats);
+  MT_CHECK_LAUNCH("cc_label3d (count)");
+  return MT_OK;
+}
+
+extern "C" int mt_cc_remove(uint8_t* seg, int D, int H, int W, const int32_t* labels, const int32_t* sizes, const int32_t* stats,
+                            double volume_per_voxel, int use_min_size, double min_size, int32_t* removed, mt_stream_t stream) {
+  MT_REQUIRE(seg && labels && sizes && stats && removed, "cc_remove: null pointer");
+  MT_REQUIRE(D > 0 && H > 0 && W > 0, "cc_remove: bad shape %d x %d x %d", D, H, W);
+  const long V = (long)D * H * W;
+  MT_REQUIRE(V <= (long)INT32_MAX, "cc_remove: %ld voxels exceed the int32 index range", V);
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(removed, 0, sizeof(int32_t), s) != hipSuccess) {
+    mt_set_error("cc_remove: hipMemsetAsync failed");
+    return MT_EHIP;
+  }
+  hipLaunchKernelGGL(cc_remove_kernel, dim3(cc_stream_blocks(V)), dim3(CC_THREADS), 0, s, seg, labels, sizes, V, stats,
+                     volume_per_voxel, min_size, use_min_size, removed);
+  MT_CHECK_LAUNCH("cc_remove");
+  return MT_OK;
+}

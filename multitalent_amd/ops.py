@@ -7,6 +7,7 @@ storage of the mixed-precision mode — float16 (activations) / bfloat16 (gradie
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -658,6 +659,60 @@ def downsample_seg_nearest(seg, out_spatial, remove_minus_one=False, out=None):
     _lib.check(_lib.load().mt_downsample_seg_nearest(_ptr(seg), B * Cn, D, H, W, _ptr(out), *[int(i) for i in out_spatial],
                                                     int(remove_minus_one), _stream()), 'downsample_seg_nearest')
     return out
+
+
+CC_MAX_VOXELS = 2 ** 31 - 1      # mt_cc_*: int32 linear indices
+
+
+def cc_check_shape(shape):
+    """Shape rules of mt_cc_label3d / mt_cc_remove, checked on the shape alone (nothing is read or allocated)."""
+    shape = tuple(int(i) for i in shape)
+    if len(shape) != 3:
+        raise ValueError("connected components: a 3-D label volume [D, H, W] is expected, got shape %s" % (shape,))
+    if shape[0] * shape[1] * shape[2] > CC_MAX_VOXELS:
+        raise ValueError("connected components: %d voxels exceed the int32 index range of the device labelling"
+                         % (shape[0] * shape[1] * shape[2]))
+    return shape
+
+
+def _check_cc_dev(*ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("multitalent_amd: connected-component post-processing runs on a HIP device only; there is no CPU fallback")
+
+
+def cc_label3d(seg, member, labels=None, sizes=None, stats=None):
+    """seg: [D, H, W] uint8 device tensor (contiguous); member: 256 host entries, non-zero = in the mask.
+    -> (labels, sizes, stats) int32 device tensors [D, H, W], [D, H, W], [2] (see mt_cc_label3d).  Nothing is synchronised."""
+    D, H, W = cc_check_shape(seg.shape)
+    _check_cc_dev(seg)
+    assert seg.dtype == torch.uint8 and seg.is_contiguous()
+    tab = np.zeros(256, dtype=np.uint8)
+    tab[:] = np.asarray(member, dtype=bool).reshape(256)
+    if labels is None:
+        labels = torch.empty((D, H, W), dtype=torch.int32, device=seg.device)
+    if sizes is None:
+        sizes = torch.empty((D, H, W), dtype=torch.int32, device=seg.device)
+    if stats is None:
+        stats = torch.empty(2, dtype=torch.int32, device=seg.device)
+    _check_cc_dev(labels, sizes, stats)
+    _lib.check(_lib.load().mt_cc_label3d(_ptr(seg), D, H, W, tab.ctypes.data_as(C.c_void_p), _ptr(labels), _ptr(sizes), _ptr(stats),
+                                         _stream()), 'cc_label3d')
+    return labels, sizes, stats
+
+
+def cc_remove(seg, labels, sizes, stats, volume_per_voxel, min_size=None, removed=None):
+    """In place on seg (uint8 device tensor [D, H, W]): zero every component of (labels, sizes, stats) from cc_label3d that
+    the reference's rule removes (see mt_cc_remove).  -> `removed`, int32 device tensor [1]: the largest removed count."""
+    D, H, W = cc_check_shape(seg.shape)
+    _check_cc_dev(seg, labels, sizes, stats)
+    assert seg.dtype == torch.uint8 and seg.is_contiguous()
+    if removed is None:
+        removed = torch.empty(1, dtype=torch.int32, device=seg.device)
+    _lib.check(_lib.load().mt_cc_remove(_ptr(seg), D, H, W, _ptr(labels), _ptr(sizes), _ptr(stats), float(volume_per_voxel),
+                                        0 if min_size is None else 1, 0.0 if min_size is None else float(min_size), _ptr(removed),
+                                        _stream()), 'cc_remove')
+    return removed
 
 
 _parse_select_env()

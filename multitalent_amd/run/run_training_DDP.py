@@ -1,7 +1,9 @@
 """`run_training_DDP` (reference run/run_training_DDP.py:30-200): one process per GPU, launched by `torch.distributed.run`
 (LOCAL_RANK from the environment or --local_rank).  Flow: configuration -> trainer(plans, fold, local_rank, ...) ->
-initialize -> [continue | pretrained weights] -> run_training -> validate.  Flags that select subsystems outside the hot path
-(`--find_lr`, cascade next-stage prediction, postprocessing search) are accepted and ignored."""
+initialize -> [continue | pretrained weights] -> run_training -> validate.  `--disable_postprocessing_on_folds` turns off the
+connected-component postprocessing search at the end of `nnUNetTrainer.validate` (the MultiTalent trainers ignore it, as the
+reference's do).  Flags that select subsystems outside the hot path (`--find_lr`, cascade next-stage prediction) are accepted
+and ignored."""
 import argparse
 import os
 

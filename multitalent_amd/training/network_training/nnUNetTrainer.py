@@ -4,8 +4,9 @@ Restates, minimally and in its own words, what the drivers call on a trainer in 
 (network_trainer.py, nnUNetTrainer.py, nnUNetTrainerV2.py, nnUNetTrainerV2_DDP.py): constructor signature, plans
 parsing, network / optimizer construction, poly learning rate, `run_iteration`, checkpoint save/load in the reference's
 file format (`.model` = torch.save(dict), `.model.pkl` = {'init','name','class','plans'}), and
-`predict_preprocessed_data_return_seg_and_softmax`, `preprocess_patient`, `validate` and the epoch-end bookkeeping that
-writes `model_best.model`.  Plotting and the postprocessing search are out of scope.  A trainer consumes any
+`predict_preprocessed_data_return_seg_and_softmax`, `preprocess_patient`, `validate` (with the connected-component
+postprocessing search `determine_postprocessing` at its end) and the epoch-end bookkeeping that writes `model_best.model`.
+Plotting is out of scope.  A trainer consumes any
 generator yielding {'data','target','properties'} batches; without one it uses device-resident synthetic batches like the
 reference's dummyLoad benchmarking trainer.
 """
@@ -438,7 +439,9 @@ class nnUNetTrainer(object):
                  segmentation_export_kwargs=None, run_postprocessing_on_folds=True):
         """nnUNetTrainer.py:526-674 (DDP: nnUNetTrainerV2_DDP.py:431-599): every validation case through the sliding window
         and the device export (probabilities never leave HBM), `summary.json` from `aggregate_scores` when the ground-truth
-        folder exists.  The connected-component postprocessing search (`run_postprocessing_on_folds`) is not on this path."""
+        folder exists, then, with `run_postprocessing_on_folds`, the connected-component postprocessing search of :648-657
+        on rank 0 (`postprocessing.json` and `<validation_folder_name>_postprocessed/`; labelling on the device).  The copy
+        of the ground truth into `gt_niftis/` for a later consolidation across folds is not done."""
         import pickle
         from ...evaluation.evaluator import aggregate_scores
         from ...inference.segmentation_export import save_segmentation_nifti_from_softmax
@@ -476,6 +479,11 @@ class nnUNetTrainer(object):
             aggregate_scores(pred_gt_tuples, labels=list(range(self.num_classes)), json_output_file=os.path.join(out, "summary.json"),
                              json_name=self.experiment_name + " val tiled %s" % str(use_sliding_window), json_author="Fabian",
                              json_task=(self.dataset_directory or "").split("/")[-1])
+            if run_postprocessing_on_folds:
+                from ...postprocessing.connected_components import determine_postprocessing
+                self.print_to_log_file("determining postprocessing")
+                determine_postprocessing(self.output_folder, self.gt_niftis_folder, validation_folder_name,
+                                         final_subf_name=validation_folder_name + "_postprocessed", debug=debug)
         self.network.train(current_mode)
         self._validation_barrier()
 
