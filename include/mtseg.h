@@ -436,6 +436,35 @@ int mt_cc_label3d(const uint8_t* seg, int D, int H, int W, const uint8_t* member
                   mt_stream_t stream);
 int mt_cc_remove(uint8_t* seg, int D, int H, int W, const int32_t* labels, const int32_t* sizes, const int32_t* stats,
                  double volume_per_voxel, int use_min_size, double min_size, int32_t* removed, mt_stream_t stream);
+/* Evaluation (evaluation/evaluator.py, evaluation/metrics.py:314-383).
+ * mt_seg_joint_hist: one pass over two contiguous uint8 label volumes of V voxels (any alignment; V is not limited to int32):
+ *   hist[remap[test[v]] * C + remap[ref[v]]] += 1, exact 64-bit counts in the device array hist[C * C] (zeroed by the call).
+ *   remap: HOST array of 256 entries, every one below C (1..256).  The confusion counts of a label entry - an int or a tuple such
+ *   as (1, 2) - are sums of cells, so all entries of a case cost one launch.  C <= 64 counts in workgroup-private LDS bins,
+ *   larger C with global atomics; integer sums: the result does not depend on the scheduling.
+ * mt_surface_distances: medpy's __surface_distances in both directions for the masks {v : member[test[v]]} (A) and
+ *   {v : member[ref[v]]} (B) of two contiguous uint8 volumes [D, H, W]; member: HOST array of 256 entries.
+ *     border(X) = X ^ binary_erosion(X, generate_binary_structure(3, connectivity)), border_value 0 (a mask voxel on a volume
+ *                 face is a border voxel), connectivity 1..3;
+ *     sds(A->B) = distance_transform_edt(~border(B), sampling = spacing)[border(A)]: for every border voxel of A, in linear
+ *                 index order, sqrt((dz sz)^2 + (dy sy)^2 + (dx sx)^2) in fp64 of the integer offsets to a nearest border voxel
+ *                 of B (exact: the nearest site is searched over all candidates in fp64); +inf when B has no border voxel.
+ *   spacing: HOST (z, y, x) doubles, NULL = (1, 1, 1).  out: device array of `capacity` doubles: sds(A->B) at [0, nA), sds(B->A)
+ *   at [nA, nA + nB); entries at or beyond `capacity` are dropped (the number of mask voxels |A| + |B| always suffices).
+ *   stats: device double[6] = (nA, max, sum) of A->B, then (nB, max, sum) of B->A; the counts are the true ones, so
+ *   nA + nB > capacity tells the caller that `out` and the maxima / sums are truncated.  Sums are formed in a fixed order without
+ *   floating-point atomics: `out` and `stats` are bit-identical from run to run.
+ *   ws: mt_surface_distances_workspace(D, H, W, capacity) bytes of device scratch, 16-byte aligned (5 bytes per voxel and
+ *   4 per entry of capacity).  D*H*W > INT32_MAX, or an axis above 32766, is rejected with MT_EINVAL before any launch.
+ * mt_select_kth: out[r] (device doubles) = the ranks[r]-th smallest (0-based) of the n non-negative doubles x, for nranks <= 8
+ *   HOST ranks: radix select on the bit patterns (non-negative doubles order as uint64).  ws: mt_select_kth_workspace(nranks)
+ *   bytes of device scratch, 8-byte aligned. */
+int mt_seg_joint_hist(const uint8_t* test, const uint8_t* ref, long V, const uint8_t* remap, int C, int64_t* hist, mt_stream_t stream);
+size_t mt_surface_distances_workspace(int D, int H, int W, long capacity);
+int mt_surface_distances(const uint8_t* test, const uint8_t* ref, int D, int H, int W, const uint8_t* member, const double* spacing,
+                         int connectivity, double* out, long capacity, double* stats, void* ws, size_t ws_bytes, mt_stream_t stream);
+size_t mt_select_kth_workspace(int nranks);
+int mt_select_kth(const double* x, long n, const long* ranks, int nranks, double* out, void* ws, size_t ws_bytes, mt_stream_t stream);
 /* ---- device-side target preparation ----------------------------------------
  * Deep-supervision label pyramid: DownsampleSegForDSTransform2 / downsample_seg_for_ds_transform2 (downsampling.py:70-104,
  * order 0 = nearest through batchgenerators' resize_segmentation -> skimage.transform.resize(order 0, mode "edge") ->

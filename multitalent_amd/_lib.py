@@ -124,6 +124,11 @@ SIGNATURES = {
     'mt_resample_classify': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _l, _l, _l, _i, _i, _i, _vp]),
     'mt_cc_label3d': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'mt_cc_remove': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _i, _d, _vp, _vp]),
+    'mt_seg_joint_hist': (_i, [_vp, _vp, _l, _vp, _i, _vp, _vp]),
+    'mt_surface_distances_workspace': (_sz, [_i, _i, _i, _l]),
+    'mt_surface_distances': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _l, _vp, _vp, _sz, _vp]),
+    'mt_select_kth_workspace': (_sz, [_i]),
+    'mt_select_kth': (_i, [_vp, _l, _vp, _i, _vp, _vp, _sz, _vp]),
     'mt_head_flip_accumulate': (_i, [_P(mt_pointwise_t), _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
     'mt_head_mirror_accumulate': (_i, [_P(mt_pointwise_t), _i, _i, _vp, _i, _f, _vp, _vp, _vp, _l, _l, _l, _i, _i, _i, _vp]),
     'mt_extract_tiles': (_i, [_vp, _i, _l, _l, _l, _vp, _i, _i, _i, _i, _vp, _vp]),

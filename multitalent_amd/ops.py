@@ -715,5 +715,120 @@ def cc_remove(seg, labels, sizes, stats, volume_per_voxel, min_size=None, remove
     return removed
 
 
+SD_MAX_AXIS = 32766             # mt_surface_distances: int16 site offsets
+SELECT_MAX_RANKS = 8
+
+
+def _check_eval_dev(*ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("multitalent_amd: the evaluation kernels run on a HIP device only; there is no CPU fallback")
+
+
+def seg_joint_hist(test, ref, remap, num_classes, hist=None):
+    """test, ref: contiguous uint8 device tensors of the same shape (any number of axes); remap: 256 host entries in
+    0..num_classes-1.  -> hist, int64 device tensor [num_classes, num_classes]: hist[i, j] = #{v : remap[test[v]] == i and
+    remap[ref[v]] == j}, exact (see mt_seg_joint_hist).  Nothing is synchronised."""
+    if tuple(test.shape) != tuple(ref.shape):
+        raise ValueError("seg_joint_hist: shape mismatch: %s and %s" % (tuple(test.shape), tuple(ref.shape)))
+    Cn = int(num_classes)
+    if not 1 <= Cn <= 256:
+        raise ValueError("seg_joint_hist: num_classes %d outside 1..256" % Cn)
+    tab = np.asarray(remap).reshape(256)
+    if tab.min() < 0 or tab.max() >= Cn:
+        raise ValueError("seg_joint_hist: remap entries must lie in 0..%d" % (Cn - 1))
+    tab = np.ascontiguousarray(tab, dtype=np.uint8)
+    _check_eval_dev(test, ref)
+    assert test.dtype == torch.uint8 and ref.dtype == torch.uint8 and test.is_contiguous() and ref.is_contiguous()
+    if test.numel() == 0:
+        raise ValueError("seg_joint_hist: empty volume")
+    if hist is None:
+        hist = torch.empty((Cn, Cn), dtype=torch.int64, device=test.device)
+    _check_eval_dev(hist)
+    assert hist.dtype == torch.int64 and hist.is_contiguous() and hist.numel() == Cn * Cn
+    _lib.check(_lib.load().mt_seg_joint_hist(_ptr(test), _ptr(ref), test.numel(), tab.ctypes.data_as(C.c_void_p), Cn, _ptr(hist),
+                                             _stream()), 'seg_joint_hist')
+    return hist
+
+
+def sd_check_shape(shape):
+    """Shape rules of mt_surface_distances, checked on the shape alone."""
+    shape = cc_check_shape(shape)
+    if max(shape) > SD_MAX_AXIS:
+        raise ValueError("surface distances: an axis of %s exceeds %d" % (shape, SD_MAX_AXIS))
+    return shape
+
+
+def surface_distances(test, ref, member, spacing=None, connectivity=1, capacity=None, out=None, stats=None, ws=None):
+    """test, ref: [D, H, W] uint8 device tensors (contiguous); member: 256 host entries, non-zero = in the mask; spacing: None
+    or (z, y, x).  -> (out, stats): out, fp64 device tensor [capacity] (default 2 * D*H*W, always enough; the number of mask
+    voxels of both volumes suffices), holds sds(test->ref) then sds(ref->test); stats, fp64 device tensor [6] = (count, max, sum)
+    per direction (see mt_surface_distances).  Nothing is synchronised."""
+    D, H, W = sd_check_shape(test.shape)
+    if tuple(ref.shape) != (D, H, W):
+        raise ValueError("surface distances: shape mismatch: %s and %s" % (tuple(test.shape), tuple(ref.shape)))
+    if connectivity not in (1, 2, 3):
+        raise ValueError("surface distances: connectivity %r (1, 2 or 3)" % (connectivity,))
+    sp = None
+    if spacing is not None:
+        sp = np.ascontiguousarray(np.asarray(spacing, dtype=np.float64).reshape(-1))
+        if sp.shape != (3,) or not np.all(np.isfinite(sp)) or not np.all(sp > 0):
+            raise ValueError("surface distances: spacing must be three positive numbers (z, y, x), got %r" % (spacing,))
+    _check_eval_dev(test, ref)
+    assert test.dtype == torch.uint8 and ref.dtype == torch.uint8 and test.is_contiguous() and ref.is_contiguous()
+    tab = np.zeros(256, dtype=np.uint8)
+    tab[:] = np.asarray(member, dtype=bool).reshape(256)
+    if out is not None:
+        capacity = out.numel()
+    elif capacity is None:
+        capacity = 2 * D * H * W
+    capacity = max(1, int(capacity))
+    if out is None:
+        out = torch.empty(capacity, dtype=torch.float64, device=test.device)
+    if stats is None:
+        stats = torch.empty(6, dtype=torch.float64, device=test.device)
+    lib = _lib.load()
+    need = lib.mt_surface_distances_workspace(D, H, W, capacity)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=test.device)
+    _check_eval_dev(out, stats, ws)
+    assert out.dtype == torch.float64 and out.is_contiguous() and stats.dtype == torch.float64 and stats.numel() == 6
+    _lib.check(lib.mt_surface_distances(_ptr(test), _ptr(ref), D, H, W, tab.ctypes.data_as(C.c_void_p),
+                                        sp.ctypes.data_as(C.c_void_p) if sp is not None else C.c_void_p(0), int(connectivity),
+                                        _ptr(out), capacity, _ptr(stats), _ptr(ws), ws.numel() * ws.element_size(), _stream()),
+               'surface_distances')
+    return out, stats
+
+
+def surface_distances_workspace(shape, capacity):
+    D, H, W = sd_check_shape(shape)
+    return int(_lib.load().mt_surface_distances_workspace(D, H, W, max(1, int(capacity))))
+
+
+def select_kth(x, ranks, out=None, ws=None):
+    """x: 1-D contiguous fp64 device tensor of non-negative values; ranks: up to 8 host ints in 0..len(x)-1.
+    -> fp64 device tensor [len(ranks)]: the ranks[r]-th smallest of x (radix select, see mt_select_kth).  Nothing is synchronised."""
+    ranks = [int(r) for r in ranks]
+    n = int(x.numel())
+    if x.dim() != 1 or n < 1:
+        raise ValueError("select_kth: a non-empty 1-D tensor is expected, got shape %s" % (tuple(x.shape),))
+    if not 1 <= len(ranks) <= SELECT_MAX_RANKS:
+        raise ValueError("select_kth: %d ranks (1..%d)" % (len(ranks), SELECT_MAX_RANKS))
+    if min(ranks) < 0 or max(ranks) >= n:
+        raise ValueError("select_kth: ranks %s outside 0..%d" % (ranks, n - 1))
+    _check_eval_dev(x)
+    assert x.dtype == torch.float64 and x.is_contiguous()
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(len(ranks), dtype=torch.float64, device=x.device)
+    if ws is None:
+        ws = torch.empty(lib.mt_select_kth_workspace(len(ranks)), dtype=torch.uint8, device=x.device)
+    _check_eval_dev(out, ws)
+    rk = (C.c_long * len(ranks))(*ranks)
+    _lib.check(lib.mt_select_kth(_ptr(x), n, C.cast(rk, C.c_void_p), len(ranks), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+               'select_kth')
+    return out
+
+
 _parse_select_env()
 _select_env = _select
