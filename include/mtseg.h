@@ -436,6 +436,27 @@ int mt_cc_label3d(const uint8_t* seg, int D, int H, int W, const uint8_t* member
                   mt_stream_t stream);
 int mt_cc_remove(uint8_t* seg, int D, int H, int W, const int32_t* labels, const int32_t* sizes, const int32_t* stats,
                  double volume_per_voxel, int use_min_size, double min_size, int32_t* removed, mt_stream_t stream);
+/* Cropping a case to its non-zero region (preprocessing/cropping.py:23-116; preprocessing/device_cropping.py).
+ * mt_nonzero_mask: mask[v] = 1 when any of the C channels of the contiguous float32 data[C][V] is != 0 at v, else 0 (:23-29 before
+ *   the hole filling).  Numpy's rule, decided on the bit pattern ((bits & 0x7fffffff) != 0): NaN, +-inf and denormals are non-zero,
+ *   -0.0 is zero, whatever the denormal mode.  Any V, any alignment of mask (data: 4 bytes).
+ * mt_fill_holes3d: in place on the contiguous uint8 volume mask[D, H, W]:  mask = scipy.ndimage.binary_fill_holes(mask != 0)  with
+ *   scipy's default structure (face neighbours only), values 0 / 1: the 6-connected components of the background are labelled with
+ *   the launches of mt_cc_label3d, and a component is filled exactly when none of its voxels lies on a face of the volume (with an
+ *   axis of length 1 every voxel does, and nothing is filled).  bbox: device int32[7] = lo_d, hi_d, lo_h, hi_h, lo_w, hi_w of the
+ *   result (hi exclusive, get_bbox_from_mask's convention) and its number of set voxels; a count of 0 means an empty mask, the box
+ *   is then unspecified.  Integer atomics only: mask and bbox are bit-identical from run to run.
+ *   ws: mt_fill_holes3d_workspace(D, H, W) bytes of device scratch, 16-byte aligned (4 bytes per voxel + 16); too small a workspace
+ *   is MT_EWORKSPACE, D*H*W > INT32_MAX is MT_EINVAL, both before any launch.
+ * mt_crop_nonzero: one pass over the HOST box[6] = lo_d, hi_d, lo_h, hi_h, lo_w, hi_w:  out[c] = data[c][box] bit for bit (C channels,
+ *   NaN payloads included), and the segmentation of :98-115.  seg_in == NULL: seg_out is int8 [1][box], 0 inside the mask and
+ *   nonzero_label (an int8 value) outside.  Otherwise seg_in is float32 [CS][D, H, W] and seg_out float32 [CS][box]:
+ *   seg_out[c] = nonzero_label where seg_in[c] == 0 and mask == 0, else seg_in[c].  D*H*W > INT32_MAX is MT_EINVAL. */
+int mt_nonzero_mask(const float* data, int C, long V, uint8_t* mask, mt_stream_t stream);
+size_t mt_fill_holes3d_workspace(int D, int H, int W);
+int mt_fill_holes3d(uint8_t* mask, int D, int H, int W, int32_t* bbox, void* ws, size_t ws_bytes, mt_stream_t stream);
+int mt_crop_nonzero(const float* data, int C, int D, int H, int W, const uint8_t* mask, const int32_t* box /* host, 6 */, float* out,
+                    const float* seg_in /* NULL or [CS][D, H, W] */, int CS, void* seg_out, float nonzero_label, mt_stream_t stream);
 /* Evaluation (evaluation/evaluator.py, evaluation/metrics.py:314-383).
  * mt_seg_joint_hist: one pass over two contiguous uint8 label volumes of V voxels (any alignment; V is not limited to int32):
  *   hist[remap[test[v]] * C + remap[ref[v]]] += 1, exact 64-bit counts in the device array hist[C * C] (zeroed by the call).

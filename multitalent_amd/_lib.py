@@ -124,6 +124,10 @@ SIGNATURES = {
     'mt_resample_classify': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _l, _l, _l, _i, _i, _i, _vp]),
     'mt_cc_label3d': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'mt_cc_remove': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _i, _d, _vp, _vp]),
+    'mt_nonzero_mask': (_i, [_vp, _i, _l, _vp, _vp]),
+    'mt_fill_holes3d_workspace': (_sz, [_i, _i, _i]),
+    'mt_fill_holes3d': (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'mt_crop_nonzero': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp]),
     'mt_seg_joint_hist': (_i, [_vp, _vp, _l, _vp, _i, _vp, _vp]),
     'mt_surface_distances_workspace': (_sz, [_i, _i, _i, _l]),
     'mt_surface_distances': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _l, _vp, _vp, _sz, _vp]),

@@ -1,8 +1,9 @@
 """One case end to end on the device (SURVEY §3.2 call stack, predict_MultiTalent.py:222-266 + preprocessing.py:226-311 +
 segmentation_export.py:27-160): cropped CT -> resample to the plan spacing + clip/z-score -> sliding window (Gaussian weighting,
 optional mirroring) -> probabilities resampled to the original grid, thresholded per region and re-inserted into the uncropped
-volume.  The volume never leaves HBM between the stages; reading / cropping the image and writing the NIfTI stay with the
-caller (SimpleITK)."""
+volume.  The volume never leaves HBM between the stages.  The crop to the non-zero region in front of this chain is on the
+device too (`preprocessing.device_cropping.crop_to_nonzero`, which `GenericPreprocessor.preprocess_test_case` uses); reading the
+image and writing the NIfTI stay with the caller (SimpleITK)."""
 import numpy as np
 
 from ..preprocessing.device_preprocessing import resample_and_normalize_ct
@@ -14,7 +15,9 @@ def predict_case_on_device(network, cropped_data, properties, target_spacing, in
                            regions_class_order=None, do_mirroring=True, mirror_axes=(0, 1, 2), step_size=0.5,
                            transpose_forward=(0, 1, 2), force_separate_z=None, tile_shard=None, verbose=False,
                            transpose_backward=None, mixed_precision=True):
-    """cropped_data: [C, X, Y, Z] (numpy or device tensor) already transposed by `transpose_forward`; properties: the case's
+    """The chain: `device_cropping.crop_to_nonzero` (the caller's, see above) -> `resample_and_normalize_ct` -> `predict_3D` ->
+    `resample_and_classify`.
+    cropped_data: [C, X, Y, Z] (numpy or device tensor) already transposed by `transpose_forward`; properties: the case's
     dict (`original_spacing`, `size_after_cropping`, `original_size_of_raw_data`, `crop_bbox`).  Returns the uint8 label volume
     (device tensor, shape `original_size_of_raw_data`) and the properties with the resampling entries filled in.
     mixed_precision: the reference's predict default (predict_MultiTalent.py `--disable_mixed_precision` turns it off); False = the fp32 parity path."""

@@ -715,6 +715,98 @@ def cc_remove(seg, labels, sizes, stats, volume_per_voxel, min_size=None, remove
     return removed
 
 
+CROP_MAX_VOXELS = CC_MAX_VOXELS  # mt_fill_holes3d / mt_crop_nonzero: int32 linear indices
+
+
+def crop_check_shape(shape):
+    """Shape rules of mt_fill_holes3d / mt_crop_nonzero for a [D, H, W] volume, checked on the shape alone."""
+    shape = tuple(int(i) for i in shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError("cropping: a non-empty 3-D volume [D, H, W] is expected, got shape %s" % (shape,))
+    if shape[0] * shape[1] * shape[2] > CROP_MAX_VOXELS:
+        raise ValueError("cropping: %d voxels exceed the int32 index range of the device labelling"
+                         % (shape[0] * shape[1] * shape[2]))
+    return shape
+
+
+def _check_crop_dev(*ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("multitalent_amd: cropping to the non-zero region runs on a HIP device only; there is no CPU fallback")
+
+
+def nonzero_mask(data, mask=None):
+    """data: [C, ...] float32 device tensor (contiguous) -> uint8 device tensor data.shape[1:]: 1 where any channel is != 0
+    (numpy's rule on the bit pattern, see mt_nonzero_mask).  `mask` may have any alignment.  Nothing is synchronised."""
+    _check_crop_dev(data)
+    assert data.dtype == torch.float32 and data.is_contiguous() and data.dim() >= 2
+    Cn = int(data.shape[0])
+    V = int(data.numel()) // max(Cn, 1)
+    if Cn < 1 or V < 1:
+        raise ValueError("nonzero_mask: empty input of shape %s" % (tuple(data.shape),))
+    if mask is None:
+        mask = torch.empty(tuple(data.shape[1:]), dtype=torch.uint8, device=data.device)
+    _check_crop_dev(mask)
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == V
+    _lib.check(_lib.load().mt_nonzero_mask(_ptr(data), Cn, V, _ptr(mask), _stream()), 'nonzero_mask')
+    return mask
+
+
+def fill_holes3d(mask, bbox=None, ws=None):
+    """In place on mask ([D, H, W] uint8 device tensor, contiguous): scipy.ndimage.binary_fill_holes(mask != 0) as 0 / 1.
+    -> (mask, bbox): bbox int32 device tensor [7] = lo_d, hi_d, lo_h, hi_h, lo_w, hi_w (hi exclusive) and the number of set voxels
+    (see mt_fill_holes3d).  ws: optional uint8 device scratch of at least fill_holes3d_workspace bytes.  Nothing is synchronised."""
+    D, H, W = crop_check_shape(mask.shape)
+    _check_crop_dev(mask)
+    assert mask.dtype == torch.uint8 and mask.is_contiguous()
+    need = int(_lib.load().mt_fill_holes3d_workspace(D, H, W))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=mask.device)
+    if bbox is None:
+        bbox = torch.empty(7, dtype=torch.int32, device=mask.device)
+    _check_crop_dev(ws, bbox)
+    assert bbox.dtype == torch.int32 and bbox.is_contiguous() and bbox.numel() == 7
+    _lib.check(_lib.load().mt_fill_holes3d(_ptr(mask), D, H, W, _ptr(bbox), _ptr(ws), ws.numel() * ws.element_size(), _stream()),
+               'fill_holes3d')
+    return mask, bbox
+
+
+def fill_holes3d_workspace(shape):
+    D, H, W = crop_check_shape(shape)
+    return int(_lib.load().mt_fill_holes3d_workspace(D, H, W))
+
+
+def crop_nonzero(data, mask, box, seg=None, nonzero_label=-1):
+    """data: [C, D, H, W] float32, mask: [D, H, W] uint8, seg: None or [CS, D, H, W] float32 — contiguous device tensors; box: six host
+    ints lo_d, hi_d, lo_h, hi_h, lo_w, hi_w.  -> (data[:, box] bit for bit, seg): int8 [1, box] (0 inside the mask, nonzero_label
+    outside) without `seg`, else float32 [CS, box] (see mt_crop_nonzero).  Nothing is synchronised."""
+    D, H, W = crop_check_shape(mask.shape)
+    _check_crop_dev(data, mask)
+    assert data.dtype == torch.float32 and data.is_contiguous() and data.dim() == 4 and tuple(data.shape[1:]) == (D, H, W)
+    assert mask.dtype == torch.uint8 and mask.is_contiguous()
+    b = np.ascontiguousarray(np.asarray(box, dtype=np.int64).reshape(6))
+    dims = (D, D, H, H, W, W)
+    if any(b[2 * a] < 0 or b[2 * a] >= b[2 * a + 1] or b[2 * a + 1] > dims[2 * a] for a in range(3)):
+        raise ValueError("crop_nonzero: box %s outside the volume %s" % (b.tolist(), (D, H, W)))
+    b = b.astype(np.int32)
+    bs = (int(b[1] - b[0]), int(b[3] - b[2]), int(b[5] - b[4]))
+    out = torch.empty((int(data.shape[0]),) + bs, dtype=torch.float32, device=data.device)
+    if seg is None:
+        if float(nonzero_label) != int(nonzero_label) or not -128 <= int(nonzero_label) <= 127:
+            raise ValueError("crop_nonzero: nonzero_label %r is not an int8 value" % (nonzero_label,))
+        seg_out = torch.empty((1,) + bs, dtype=torch.int8, device=data.device)
+        seg_ptr, CS = None, 0
+    else:
+        _check_crop_dev(seg)
+        assert seg.dtype == torch.float32 and seg.is_contiguous() and seg.dim() == 4 and tuple(seg.shape[1:]) == (D, H, W)
+        CS = int(seg.shape[0])
+        seg_out = torch.empty((CS,) + bs, dtype=torch.float32, device=data.device)
+        seg_ptr = _ptr(seg)
+    _lib.check(_lib.load().mt_crop_nonzero(_ptr(data), int(data.shape[0]), D, H, W, _ptr(mask), b.ctypes.data_as(C.c_void_p), _ptr(out),
+                                           seg_ptr, CS, _ptr(seg_out), float(nonzero_label), _stream()), 'crop_nonzero')
+    return out, seg_out
+
+
 SD_MAX_AXIS = 32766             # mt_surface_distances: int16 site offsets
 SELECT_MAX_RANKS = 8
 

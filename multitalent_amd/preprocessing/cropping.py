@@ -1,6 +1,7 @@
-"""Reading a case and cropping it to its non-zero region (reference preprocessing/cropping.py:23-155) — the host-side front of
-`preprocess_patient`.  binary_fill_holes (scipy) and file reading stay on the host; everything after the crop runs on the device
-(preprocessing.GenericPreprocessor.resample_and_normalize)."""
+"""Reading a case and cropping it to its non-zero region (reference preprocessing/cropping.py:23-155) on the host, with scipy's
+binary_fill_holes.  `preprocess_patient` reads the files with `load_case_from_list_of_files` and crops on the device
+(`device_cropping.py`, same names and signatures); the croppers here are the host statement of the same semantics — what the
+device path is tested against, and what a volume beyond the device labelling's int32 index range still goes through."""
 from collections import OrderedDict
 
 import numpy as np

@@ -6,7 +6,7 @@ skimage.transform.resize(order=3, mode='edge', anti_aliasing=False) is scipy.ndi
 grid_mode=True): the volume is edge-padded by 12 voxels, spline-prefiltered and sampled at x = (o + 0.5) * in/out - 0.5.  Here:
 replicate padding (torch glue), `mt_spline_prefilter3`, `mt_affine_sample` (cubic, diagonal matrix).  The prefilter initialises
 with mirror boundaries where scipy uses its 'nearest' rule; twelve voxels of edge padding damp the difference to z^12 = 1.4e-7.
-Not on the device: cropping to the non-zero region (scipy binary_fill_holes) and file I/O — they stay with the caller."""
+The crop to the non-zero region in front of this is `device_cropping.py` (also on the device); file I/O stays with the caller."""
 import numpy as np
 import torch
 import torch.nn.functional as F

@@ -367,7 +367,7 @@ class nnUNetTrainer(object):
 
     # ---- unseen data (nnUNetTrainer.py:417-443) -------------------------------------------------------------------
     def preprocess_patient(self, input_files, return_device=False):
-        """Read + crop the case on the host, resample to the plan's spacing and normalise on the device.  Returns
+        """Read the case on the host; crop to the non-zero region, resample to the plan's spacing and normalise on the device.  Returns
         (data [C, X, Y, Z] float32, seg, properties) like the reference (numpy; `return_device=True` keeps the volume in HBM)."""
         name = self.plans.get('preprocessor_name') or "GenericPreprocessor"
         if name != "GenericPreprocessor":
