@@ -188,12 +188,13 @@ int mt_conv3d_bwd_weight_io_supported(const mt_conv3d_t* p, const mt_src_t* ysrc
  * limit and the CU count that sizes persistent grids, keyed by the current HIP device (one process may drive several GPUs).
  * Rounds 1 - 5 had 39 MT_* environment switches and mt_set_option in here; the A/Bs they served are closed, the losing
  * kernels are deleted or unreachable, and the families tests still compare are the MT_SEL_* fields above.
- * The HOST side above this ABI (multitalent_amd/engine.py, ops.py, inference/, bench.py) has its own knobs: MT_BF16_STORAGE (0: fp32
- * storage in mixed precision), MT_ACT_STORAGE (fp16 | bf16), MT_BF16_MIN_VOXELS, MT_BWDW_STREAMS, MT_FUSED_LOSS, MT_STEP_GRAPH, MT_IO_DEBUG
- * (1: print every launch that needed an mt_cast), MT_SELECT ("x16=off,wino=force,...": default mt_conv3d_t.select of the process, for A/B
- * runs of whole steps), MT_FORCE_REDUCER, MT_BENCH_ONE_GPU (bench.py: all ranks on cuda:0 over gloo), MT_LIB_VARIANT.
- * Which workgroup computes which tile (block id -> XCD -> tile order) is a compile-time choice (-DMT_TILE_ORDER=0 builds
- * the round-2 order for A/B measurements); results do not depend on it. */
+ * The HOST side above this ABI (multitalent_amd/) reads four environment variables, and no others: MT_SELECT ("x16=off,wino=force,...":
+ * default mt_conv3d_t.select of the process, for A/B runs of whole steps), MT_LIB_VARIANT (file name of an instrumented build of this
+ * library), MT_FORCE_REDUCER (1: the bucketed side-stream all-reduce also at world size 1) and MT_BWDW_STREAMS (0: weight gradients on
+ * the compute stream, which the per-kernel profiles need; results are bit-identical).  bench.py adds MT_BENCH_ONE_GPU (all ranks on
+ * cuda:0 over gloo).  The experiment switches of rounds 2 - 6 and the opt-in HIP-graph step are gone (DESIGN.md 0, 3 and 6 keep
+ * their measurements).  Which workgroup computes which tile (block id -> XCD -> tile order) is fixed; results do not
+ * depend on it. */
 
 /* Device probe (SYNCHRONOUS, call once per device before the first launch; the Python binding does so when it loads the
  * library): checks that the current device is gfx950 and that raw buffer loads behave the way the vector-load kernels assume —

@@ -23,47 +23,24 @@
 
 
 // Block -> (spatial tile, output-channel tile).  Workgroups are dispatched in linear order (x fastest, then y) round-robin over the
-// eight XCDs, each with its own L2.  MT_TILE_ORDER 1: an XCD walks a CONTIGUOUS range of (spatial tile, channel tile) pairs with
+// eight XCDs, each with its own L2.  An XCD walks a CONTIGUOUS range of (spatial tile, channel tile) pairs with
 // the channel tile fastest — all channel tiles of a spatial tile read the same input patch while it is in that L2 — and the
 // spatial tiles in the order D, H, W (W slowest): the tiles resident on an XCD at one time then form a compact D x H block at one
 // w position, so the halo rows (TH + 2 rows fetched for TH outputs: the expensive direction) are shared in L2 instead of being
-// fetched again a whole D x W plane later.  0: the previous order (channel tile = blockIdx.y slowest; D, W, H).
-#ifndef MT_TILE_ORDER
-#define MT_TILE_ORDER 1
-#endif
+// fetched again a whole D x W plane later.
 __device__ __forceinline__ int mt_block_decode(int& ntile) {
-#if MT_TILE_ORDER
   const int ny = (int)gridDim.y;
   const int b = mt_xcd_remap((int)(blockIdx.x + gridDim.x * blockIdx.y), (int)(gridDim.x * ny));
   const int t = b / ny;
   ntile = b - t * ny;
   return t;
-#else
-  ntile = blockIdx.y;
-  return mt_xcd_remap(blockIdx.x, gridDim.x);
-#endif
 }
-// spatial tile index -> (td, th, tw, sample); OLD = the kernel's order under MT_TILE_ORDER 0 (0: D, W, H; 1: W, H, D)
-template <int OLD = 0>
+// spatial tile index -> (td, th, tw, sample)
 __device__ __forceinline__ void mt_tile_coords(int tile, int tilesD, int tilesH, int tilesW, int& td, int& th, int& tw, int& nb) {
-#if MT_TILE_ORDER
   td = tile % tilesD; tile /= tilesD;
   th = tile % tilesH; tile /= tilesH;
   tw = tile % tilesW;
   nb = tile / tilesW;
-#else
-  if constexpr (OLD == 0) {
-    td = tile % tilesD; tile /= tilesD;
-    tw = tile % tilesW; tile /= tilesW;
-    th = tile % tilesH;
-    nb = tile / tilesH;
-  } else {
-    tw = tile % tilesW; tile /= tilesW;
-    th = tile % tilesH; tile /= tilesH;
-    td = tile % tilesD;
-    nb = tile / tilesD;
-  }
-#endif
 }
 
 // Split the concatenated input channels (C0 | C1) into chunks of <= ck channels that never straddle
@@ -346,7 +323,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(const ConvKParams P) {
   const int li = lane & 31, lhalf = lane >> 5;
 
   int ntile, td, th, tw, nb;
-  mt_tile_coords<1>(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
+  mt_tile_coords(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
   const int sb = (td * P.tilesH + th) * P.tilesW + tw;
 
   // FAST: 3x3x3, stride 1, pad 1, no zero insertion -> the whole tile geometry is compile-time
@@ -794,7 +771,7 @@ __global__ __launch_bounds__(256) void conv_fast_kernel(const ConvKParams P) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lhalf = lane >> 5;
   int ntile, td, th, tw, nb;
-  mt_tile_coords<1>(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
+  mt_tile_coords(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
   const int sb = (td * P.tilesH + th) * P.tilesW + tw;
   const int od0 = td * TD, oh0 = th * TH, ow0 = tw * TW;
 
@@ -938,7 +915,7 @@ __global__ __launch_bounds__(256) void conv_fast_strided_kernel(const ConvKParam
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lhalf = lane >> 5;
   int by, td, th, tw, nb;
-  mt_tile_coords<1>(mt_block_decode(by), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
+  mt_tile_coords(mt_block_decode(by), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
   const int dm = wave & 1, nt2 = wave >> 1;
   const int ntile_raw = by * 2 + nt2;
   const bool nt_ok = ntile_raw * 32 < c.Cout;           // wave-uniform: an odd number of 32-channel tiles leaves one wave idle
@@ -1061,7 +1038,7 @@ __global__ __launch_bounds__(256) void conv_tapsplit_kernel(const ConvKParams P)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lhalf = lane >> 5;
   int ntile, td, th, tw, nb;
-  mt_tile_coords<1>(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
+  mt_tile_coords(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
   const int sb = (td * P.tilesH + th) * P.tilesW + tw;
   const int od0 = td * TD, oh0 = th * TH, ow0 = tw * TW;
   // M tile row li -> voxel (dm, r, col) = (li>>4, (li>>2)&3, li&3)
@@ -1228,7 +1205,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(const ConvKParams P) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lhalf = lane >> 5;
   int ntile, td, th, tw, nb;
-  mt_tile_coords<1>(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
+  mt_tile_coords(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
   const int sb = (td * P.tilesH + th) * P.tilesW + tw;
   const int od0 = td * TD, oh0 = th * TH, ow0 = tw * TW;
   stem_stage<TD, TH, TW>(xs, c, nb, od0, oh0, ow0, tid);
@@ -1723,7 +1700,7 @@ __global__ __launch_bounds__(256) void conv_rt_kernel(const ConvKParams P) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lhalf = lane >> 5;
   int ntile, td, th, tw, nb;
-  mt_tile_coords<1>(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
+  mt_tile_coords(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
   const int sb = (td * P.tilesH + th) * P.tilesW + tw;
   const int LD = (TD - 1) * c.SD + c.KD, LH = (TH - 1) * c.SH + c.KH, LW = (TW - 1) * c.SW + c.KW;
   const int od0 = td * TD, oh0 = th * TH, ow0 = tw * TW;
@@ -1876,7 +1853,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lhalf = lane >> 5;
   int ntile, td, th, tw, nb;
-  mt_tile_coords<1>(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
+  mt_tile_coords(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
   const int md0 = td * TD, mh0 = th * TH, mw0 = tw * TW;
 
   // this wave's M tile: dm = wave/2, rows (wave%2)*2 + {0,1}, 16 columns
@@ -2075,7 +2052,7 @@ __global__ __launch_bounds__(256) void conv_bwdd_strided_ks_kernel(const ConvKPa
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, lhalf = lane >> 5;
   int ntile, td, th, tw, nb;
-  mt_tile_coords<1>(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
+  mt_tile_coords(mt_block_decode(ntile), P.tilesD, P.tilesH, P.tilesW, td, th, tw, nb);
   const int md0 = td * TD, mh0 = th * TH, mw0 = tw * TW;
   // M row li -> dY position (li >> 4, (li >> 2) & 3, li & 3); the lane's eight channels of a chunk start at lhalf * 8, this wave's two
   // at + 2 wave (the MFMA pairs channel lhalf * 8 + k of both lane halves)
@@ -2174,8 +2151,6 @@ static size_t cfg_lds(const ConvCfg& g, const mt_conv3d_t* p) {
 }
 // choose the tile shape with the least padded work that fits LDS; prefer >=2 workgroups per CU
 static int pick_cfg(const mt_conv3d_t* p) {
-  constexpr int force = -1;
-  if (force >= 0 && cfg_lds(kCfgs[force], p) <= 160 * 1024) return force;
   int best = -1; double bestcost = 1e300;
   for (int i = 0; i < (int)(sizeof(kCfgs) / sizeof(kCfgs[0])); ++i) {
     const ConvCfg& g = kCfgs[i];
@@ -2211,19 +2186,15 @@ static int conv_fast_vec(const mt_conv3d_t* p);
 // mt_conv3d_t.select field as the legacy three-way switch: 0 = never this family, 1 = the library's policy, 2 = wherever eligible
 static inline int mt_sel3(const mt_conv3d_t* p, int shift) { const unsigned v = MT_SEL_GET(p->select, shift); return v == MT_SEL_OFF ? 0 : v == MT_SEL_FORCE ? 2 : 1; }
 static ConvPlan conv_plan(const mt_conv3d_t* p) {
-  constexpr int use_v2 = 1, use_rt = 1;
   ConvPlan pl; pl.kind = CONV_GENERIC; pl.cfg = pick_cfg(p);
   if (p->mma == 1) {                      // bf16 matrix inputs where the bf16 kernel serves the problem; fp32 kernels elsewhere
     const int bc = conv_bf16_cfg(p);
     if (bc >= 0) { pl.kind = CONV_BF16; pl.cfg = bc; return pl; }
   }
-  if (conv_is_fast(p) && use_v2 && p->osD <= 0 && p->nsrc == 1 && p->Cin == 1 && p->csplit >= p->Cout &&
-      (double)p->Do * p->Ho * p->Wo * p->ocs0 * 4.0 < 2147483648.0) {
-    constexpr int use_stem = 1;
-    if (use_stem) { pl.kind = CONV_STEM; pl.cfg = 0; return pl; }
-  }
-  if (conv_is_fast(p) && use_v2 && pl.cfg >= 0 && pl.cfg <= 2 && p->osD <= 0 && conv_wino_ok(p)) { pl.kind = CONV_WINO; return pl; }
-  if (conv_is_fast(p) && use_v2 && pl.cfg >= 0 && pl.cfg <= 2 && p->osD <= 0) {
+  if (conv_is_fast(p) && p->osD <= 0 && p->nsrc == 1 && p->Cin == 1 && p->csplit >= p->Cout &&
+      (double)p->Do * p->Ho * p->Wo * p->ocs0 * 4.0 < 2147483648.0) { pl.kind = CONV_STEM; pl.cfg = 0; return pl; }
+  if (conv_is_fast(p) && pl.cfg >= 0 && pl.cfg <= 2 && p->osD <= 0 && conv_wino_ok(p)) { pl.kind = CONV_WINO; return pl; }
+  if (conv_is_fast(p) && pl.cfg >= 0 && pl.cfg <= 2 && p->osD <= 0) {
     pl.kind = CONV_FAST;
     // low-resolution stages: fewer than two workgroups per CU -> split the taps over the waves instead
     const int use_ts = mt_sel3(p, MT_SEL_TAPSPLIT);
@@ -2232,11 +2203,8 @@ static ConvPlan conv_plan(const mt_conv3d_t* p) {
     if (use_ts && wgs < 300 && p->csplit >= p->Cout && (double)p->Do * p->Ho * p->Wo * p->ocs0 * 4.0 < 2147483648.0) pl.kind = CONV_TAPSPLIT;
     return pl;
   }
-  if (conv_is_133(p) && use_v2 && pl.cfg >= 0 && pl.cfg <= 2 && p->osD <= 0 && p->Cin >= 8) {      // compile-time taps instead of conv_rt
-    constexpr int use133 = 1;
-    if (use133) { pl.kind = CONV_FAST; return pl; }
-  }
-  if (use_rt && conv_fast_strided_ok(p)) {
+  if (conv_is_133(p) && pl.cfg >= 0 && pl.cfg <= 2 && p->osD <= 0 && p->Cin >= 8) { pl.kind = CONV_FAST; return pl; }      // compile-time taps instead of conv_rt
+  if (conv_fast_strided_ok(p)) {
     pl.kind = CONV_FAST_STRIDED; pl.cfg = 0;
     // fewer workgroups than CUs in the 2x4x8 x 64-channel tiling: one 32-voxel tile x 32 channels per workgroup, taps over the waves
     const int g_tapsplit = mt_sel3(p, MT_SEL_TAPSPLIT);
@@ -2246,7 +2214,7 @@ static ConvPlan conv_plan(const mt_conv3d_t* p) {
     if (g_tapsplit && (wgs < 256 || g_tapsplit >= 2) && inst) pl.kind = CONV_TAPSPLIT;
     return pl;
   }
-  if (use_rt && conv_rt_ok(p)) {
+  if (conv_rt_ok(p)) {
     const int i = pick_rt_cfg(p);
     if (i >= 0) { pl.kind = CONV_RT; pl.cfg = i; return pl; }
   }
@@ -2307,8 +2275,6 @@ static bool conv_is_fast(const mt_conv3d_t* p) {
 
 // FAST v2 eligibility: FAST geometry + 8-byte alignment of every source for the 2-channel staging loads
 static int conv_fast_vec(const mt_conv3d_t* p) {
-  constexpr int force1 = 0;
-  if (force1) return 1;
   for (int i = 0; i < p->nsrc; ++i) {
     const mt_src_t& s = p->src[i];
     if ((s.cs & 1) || (s.C & 1) || (((uintptr_t)s.ptr) & (mt_is16(s.dtype) ? 3 : 7))) return 1;   // a channel pair = one 8 / 4-byte load
@@ -2492,14 +2458,12 @@ static int conv_bf16_cfg(const mt_conv3d_t* p) {
   if ((double)p->Do * p->Ho * p->Wo * p->ocs0 * 4.0 >= 2147483648.0) return -1;            // 31-bit store offsets per sample
   if (p->csplit < p->Cout && (double)p->Do * p->Ho * p->Wo * p->ocs1 * 4.0 >= 2147483648.0) return -1;
   if (mt_cdiv(p->src[0].C, FCK) + (p->nsrc == 2 ? mt_cdiv(p->src[1].C, FCK) : 0) > MT_MAX_CHUNKS) return -1;
-  constexpr int force = -1;
   int best = -1; double bestcost = 1e300;
   for (int i = 0; i < (int)(sizeof(kBfCfgs) / sizeof(kBfCfgs[0])); ++i) {
     int TD, TH, TW; cfg_tile(kBfCfgs[i], &TD, &TH, &TW);
     const double vol = (double)mt_cdiv(p->Do, TD) * TD * mt_cdiv(p->Ho, TH) * TH * mt_cdiv(p->Wo, TW) * TW;
     const double halo = (double)(TD + 2) * (TH + 2) * (TW + 2) / ((double)TD * TH * TW);
     const double cost = vol * (0.5 + 0.5 * halo / 2.0);
-    if (i == force) { best = i; break; }
     if (cost < bestcost - 1e-9) { bestcost = cost; best = i; }
   }
   if (best < 0) return -1;
@@ -2704,11 +2668,8 @@ static int launch_gather(const mt_conv3d_t* p, hipStream_t st) {
   dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(p->Cout, 32), 1);
   const mt_src_t& S = p->src[0];
   // 16-byte loads at any alignment (dword-aligned dwordx4 buffer loads are legal and range-checked per dword: tools/ubench/oob128.hip)
-  constexpr int force_vec = 0;
-  int vec = 4;
-  if (force_vec == 1 || force_vec == 2) vec = force_vec;
-  if (vec == 2 && !((S.cs % 2) == 0 && (((uintptr_t)S.ptr) & 7) == 0)) vec = 1;
-  (void)S;
+  // (the <2> and <1> instances below are unreachable; they stay until the device code itself is cleaned up)
+  const int vec = 4;
   // gradients: bf16 -> bf16 (backward-data of a transposed convolution between two 16-bit levels), bf16 -> fp32, fp32 -> bf16
   if (gather_use_bf16(p) && p->odtype == MT_BF16) hipLaunchKernelGGL((conv_gather_kernel<4, MT_BF16, MT_BF16, true>), grid, dim3(256), 0, st, P);
   else if (gather_use_bf16(p)) hipLaunchKernelGGL((conv_gather_kernel<4, MT_BF16, MT_F32, true>), grid, dim3(256), 0, st, P);
@@ -4462,11 +4423,10 @@ extern "C" size_t mt_conv3d_bwd_weight_workspace(const mt_conv3d_t* p) {
 
 extern "C" int mt_conv3d_bwd_weight_kernel_name(const mt_conv3d_t* p, const mt_src_t* ysrc, char* buf, size_t n) {
   if (p == nullptr || ysrc == nullptr || buf == nullptr || n == 0) return MT_EINVAL;
-  constexpr int use_fast = 1;
-  if (use_fast && bwdw_is_stem(p, ysrc)) { snprintf(buf, n, "conv_bwdw_stem_kernel<%d>", ysrc->dtype); return MT_OK; }
-  const int geo = use_fast ? bwdw_fast_geo(p, ysrc) : -1;
+  if (bwdw_is_stem(p, ysrc)) { snprintf(buf, n, "conv_bwdw_stem_kernel<%d>", ysrc->dtype); return MT_OK; }
+  const int geo = bwdw_fast_geo(p, ysrc);
   if (geo < 0) { snprintf(buf, n, "conv_bwdw_kernel"); return MT_OK; }
-  if (use_fast && bwdw_use_gemm(p, ysrc)) { snprintf(buf, n, "bwdw_gemm_kernel"); return MT_OK; }
+  if (bwdw_use_gemm(p, ysrc)) { snprintf(buf, n, "bwdw_gemm_kernel"); return MT_OK; }
   if ((geo == 0 || geo == 6) && bwdw_use_tr16(p, ysrc)) { snprintf(buf, n, "conv_bwdw_tr16_kernel<%d, %d>", p->KD, conv_src_dtype(p)); return MT_OK; }
   if (geo == 0) {
     if (bwdw_use_wino(p)) snprintf(buf, n, "conv_bwdw_wino_kernel<2>");
@@ -4490,8 +4450,6 @@ extern "C" int mt_conv3d_bwd_weight_io_supported(const mt_conv3d_t* p, const mt_
   const int xdt = conv_src_dtype(p);
   if (xdt < 0 || !mt_dtype_ok(ysrc->dtype)) return 0;
   if (xdt == MT_F32 && ysrc->dtype == MT_F32) return 1;
-  constexpr int use_fast_q = 1;
-  if (!use_fast_q) return 0;
   const int ydt = ysrc->dtype;
   if (bwdw_is_stem(p, ysrc)) return (xdt == MT_F32 && ydt != MT_F16) ? 1 : 0;       // fp32 network input, fp32 | bf16 gradient
   const int geo = bwdw_fast_geo(p, ysrc);
@@ -4520,8 +4478,7 @@ extern "C" int mt_conv3d_bwd_weight(const mt_conv3d_t* p, const mt_src_t* ysrc, 
   P.c = *p;
   if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
   P.y = *ysrc;
-  constexpr int use_fast = 1;
-  if (use_fast && bwdw_is_stem(p, ysrc)) {
+  if (bwdw_is_stem(p, ysrc)) {
     P.TD = 2; P.TH = 4; P.TW = 32;
     P.tilesD = mt_cdiv(p->Do, 2); P.tilesH = mt_cdiv(p->Ho, 4); P.tilesW = mt_cdiv(p->Wo, 32);
     P.ntiles_total = P.tilesD * P.tilesH * P.tilesW * p->N;
@@ -4545,7 +4502,7 @@ extern "C" int mt_conv3d_bwd_weight(const mt_conv3d_t* p, const mt_src_t* ysrc, 
     MT_CHECK_LAUNCH("bwdw_reduce");
     return MT_OK;
   }
-  const int geo = use_fast ? bwdw_fast_geo(p, ysrc) : -1;
+  const int geo = bwdw_fast_geo(p, ysrc);
   if (geo >= 0 && bwdw_use_gemm(p, ysrc))
     return launch_bwdw_gemm(p, ysrc, dw, s_ci, s_co, s_kd, s_kh, s_kw, accumulate, workspace, workspace_bytes, (hipStream_t)stream);
   if (geo >= 0) {

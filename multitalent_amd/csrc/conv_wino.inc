@@ -64,7 +64,6 @@ __device__ __forceinline__ void wino8p_body(const ConvKParams& P) {
   const int li = lane & 31, lhalf = lane >> 5;
   const int ntile = blockIdx.y;
   const int T = P.nsb * c.N;
-#if MT_TILE_ORDER
   // The workers of one group (= one XCD whenever gridDim.x is a multiple of 8: workgroups go round-robin over the XCDs in
   // dispatch order) share a CONTIGUOUS range of the tile sequence and walk it side by side, NWK tiles per iteration, in the order
   // D, H, W: what the group holds at one time is a compact D x H block of tiles whose halo rows are fetched into that XCD's L2
@@ -75,11 +74,6 @@ __device__ __forceinline__ void wino8p_body(const ConvKParams& P) {
   const int tbase = (int)(((long)T * grp) / ngrp);
   const int lw = tbase + (int)blockIdx.x / ngrp;
   const int tend = (int)(((long)T * (grp + 1)) / ngrp);
-#else
-  const int NWK = (int)gridDim.x;
-  const int lw = mt_xcd_remap(blockIdx.x, NWK);
-  const int tend = T;
-#endif
   if (lw >= tend) return;                                // (workgroup-uniform)
   const int niter = (tend - lw + NWK - 1) / NWK;
   const int G = niter * P.nchunks;

@@ -1002,7 +1002,6 @@ extern "C" int mt_pointwise_fwd(const mt_pointwise_t* p, mt_stream_t stream) {
   MT_REQUIRE(p != nullptr, "pointwise: null params");
   MT_REQUIRE(mt_pointwise_io_supported(p), "pointwise: storage types (src %d, out %d) not taken (ask mt_pointwise_io_supported, convert with mt_cast)", p->src.dtype, p->odtype);
   const int xs = p->src.dtype, os = p->odtype;
-  const bool any16 = xs != MT_F32 || os != MT_F32;
   MT_REQUIRE(p->N > 0 && p->Db > 0 && p->Hb > 0 && p->Wb > 0 && p->Cin > 0 && p->Cout > 0, "pointwise: empty problem");
   MT_REQUIRE(p->siD >= 1 && p->siD <= 2 && p->siH >= 1 && p->siH <= 2 && p->siW >= 1 && p->siW <= 2, "pointwise: input stride must be 1 or 2");
   MT_REQUIRE(p->soD >= 1 && p->soD <= 2 && p->soH >= 1 && p->soH <= 2 && p->soW >= 1 && p->soW <= 2, "pointwise: output stride must be 1 or 2");
@@ -1020,24 +1019,19 @@ extern "C" int mt_pointwise_fwd(const mt_pointwise_t* p, mt_stream_t stream) {
   MT_REQUIRE(P.ntaps == 1 || P.ntaps == 2 || P.ntaps == 4 || P.ntaps == 8, "pointwise: unsupported tap count %d", P.ntaps);
   MT_REQUIRE(P.nchunks * PW_CK <= PW_MAXC, "pointwise: Cin = %d exceeds %d", p->Cin, PW_MAXC);
   {
-    constexpr int use_wide = 1;
-    const bool shape_ok = use_wide && P.ntaps >= 4 && p->soW == 2 && p->soH == 2 && (p->Wb % 32) == 0 && p->Cout <= 32 && (p->Cout % 2) == 0 &&
+    const bool shape_ok = P.ntaps >= 4 && p->soW == 2 && p->soH == 2 && (p->Wb % 32) == 0 && p->Cout <= 32 && (p->Cout % 2) == 0 &&
                           !p->accumulate && p->stats_part == nullptr && p->siD == 1 && p->siH == 1 && p->siW == 1;
     P.wide = 0;
     if (shape_ok && p->ocs == p->Cout && ((((uintptr_t)p->out) & 7) == 0)) P.wide = 2;                       // dense output: linear 8-byte (fp32) / 4-byte (16-bit) stores
     else if (shape_ok && (p->ocs % 4) == 0 && ((((uintptr_t)p->out) & 15) == 0)) P.wide = 1;                 // concat slot: 16 / 8-byte pieces per voxel
   }
-  const mt_src_t& S = p->src;
   // 16-byte loads whatever the alignment: a raw buffer_load_dwordx4 only needs dword alignment and range-checks per dword
   // (tools/ubench/oob128.hip); the 47-channel gradient of the heads (188-byte rows) went through eight scalar loads per chunk before
-  constexpr int force_vec = 0;
-  int vec = 4;
-  if (!any16 && (force_vec == 1 || force_vec == 2 || force_vec == 4)) vec = force_vec;
-  if (vec == 2 && !((S.cs % 2) == 0 && (((uintptr_t)S.ptr) & 7) == 0)) vec = 1;
+  // (the <NT, 2> and <NT, 1> instances below are unreachable; they stay until the device code itself is cleaned up)
+  const int vec = 4;
   hipStream_t st = (hipStream_t)stream;
   {
-    constexpr int use_head = 1;
-    if (use_head && os == MT_F32 && pw_narrow_ok(p, P)) {
+    if (os == MT_F32 && pw_narrow_ok(p, P)) {
       long blocks = (P.Vb + 255) / 256; if (blocks > 4096) blocks = 4096;
       const dim3 g2((unsigned)blocks, (unsigned)p->N);
 #define PW_NARROW(CIN_) do { if (xs == MT_F16) hipLaunchKernelGGL((pw_narrow_kernel<CIN_, MT_F16>), g2, dim3(256), 0, st, P);           \
@@ -1048,7 +1042,7 @@ extern "C" int mt_pointwise_fwd(const mt_pointwise_t* p, mt_stream_t stream) {
       MT_CHECK_LAUNCH("pointwise_narrow");
       return MT_OK;
     }
-    if (use_head && os == MT_F32 && pw_head_ok(p, P)) {
+    if (os == MT_F32 && pw_head_ok(p, P)) {
       const dim3 g1((unsigned)(P.nsb * p->N));
       if (pw_m16(p, P, false, true)) hipLaunchKernelGGL((pw_head_kernel<MT_F16, true>), g1, dim3(256), 0, st, P);
       else if (xs == MT_F16) hipLaunchKernelGGL((pw_head_kernel<MT_F16>), g1, dim3(256), 0, st, P);

@@ -67,7 +67,7 @@ class ConvNormOp(_Op):
         # stride-th voxel, backward-data = the pointwise kernel scattering to those voxels (mt_pointwise_t.scatter), backward-weight =
         # the tiled kernel.  (Until round 3 all three ran on the runtime-geometry convolution kernels.)
         self._pw_strided_geom = (not pointwise and self.kernel == (1, 1, 1) and self.stride != (1, 1, 1) and self.pad == (0, 0, 0)
-                                 and len(srcs) == 1 and os.environ.get('MT_PW_STRIDED', '1') != '0')
+                                 and len(srcs) == 1)
         self.pw_strided = False      # decided in plan(): the input size must be a multiple of the stride (the scatter's output grid)
         self.bwd_part = None         # (partials, first column): first pass of this layer's norm backward, fused into the last writer of out.grad
 
@@ -89,7 +89,7 @@ class ConvNormOp(_Op):
         self.out.spatial = self.geom.out
         Cout = self.conv.out_channels
         self.pw_strided = self._pw_strided_geom and tuple(o * st for o, st in zip(self.geom.out, self.stride)) == tuple(self.geom.inp)
-        self.mma = eng.op_mma(self.geom.out)          # bf16 matrix inputs for this layer (forward, backward-data and backward-weight)
+        self.mma = eng.mma          # bf16 matrix inputs for this layer (forward, backward-data and backward-weight)
         buf = eng.buffer(self.name + '.y', (N,) + self.geom.out + (Cout,), self._out_dtype(eng))
         if self.norm is not None:
             st = eng.buffer(self.name + '.stats', (4, N, Cout))
@@ -518,11 +518,9 @@ class HeadOp(ConvNormOp):
         """dX, dW and dbias of the head in ONE pass over (x, dlogits) (mt_head_bwd) when the head is narrow enough (<= 64 channels
         in and out: the full-resolution heads, where 47 logit channels make the separate kernels cost 3 ms of a Task100 step);
         otherwise the generic pointwise backward-data + tiled backward-weight of ConvNormOp."""
-        import os
         s0 = self.srcs[0]
         Cout = self.conv.out_channels
-        if (os.environ.get('MT_HEAD_BWD_FUSED', '1') == '0' or s0.grad is None or self.wb is None
-                or not ops.head_bwd_supported(s0.C, Cout) or self.stride != (1, 1, 1)):
+        if s0.grad is None or self.wb is None or not ops.head_bwd_supported(s0.C, Cout) or self.stride != (1, 1, 1):
             return super().backward(eng)
         g = self.out.grad
         assert g is not None and self.out.grad_init, "gradient of %s was never produced" % self.name
@@ -610,13 +608,8 @@ class Engine:
         # mixed precision: ACTIVATIONS are stored as fp16 and the forward convolutions multiply fp16 operands (the reference's autocast
         # arithmetic: 11 significand bits keep the LeakyReLU decisions of the forward pass — which is what the gradient's direction
         # hangs on, DESIGN.md 3.3 — four times closer to the exact ones than bf16 does); GRADIENTS are stored as bf16 and the backward
-        # convolutions multiply bf16 operands (fp32's exponent range: no loss scaling).  MT_BF16_STORAGE=0: fp32 storage with bf16
-        # matrix inputs only (the mode of rounds 1-3); MT_ACT_STORAGE=bf16: bf16 activations (measured: gradient cosine 0.86 instead of
-        # 0.98 on the full-size residual encoder).  bf16_min_voxels > 0 keeps the levels with fewer voxels per sample in fp32, storage
-        # and arithmetic (measured: no gain in accuracy, +2.5 ms per step: default 0).
-        self.storage_bf16 = os.environ.get('MT_BF16_STORAGE', '1') != '0'
-        self.act_storage = {'fp16': torch.float16, 'bf16': torch.bfloat16}[os.environ.get('MT_ACT_STORAGE', 'fp16')]
-        self.bf16_min_voxels = int(os.environ.get('MT_BF16_MIN_VOXELS', '0'))
+        # convolutions multiply bf16 operands (fp32's exponent range: no loss scaling).  The same at every level (bf16 activations
+        # and an fp32 floor for the small levels both measured worse).
         self._io_cache = {}
         self._fp32_copies = {}
         self._iter = 0
@@ -627,7 +620,7 @@ class Engine:
         # fusing it into the matrix-bound kernel on the chain measured 0 ... +0.3 ms per step
         # Mixed precision beside that stream: the residual-add form only (3) — the add's backward is bandwidth-bound itself, so the
         # extra sums cost nothing there (residual encoder mixed 25.48 -> 25.27 ms, fp32 unchanged: tools/r4_run47.sh)
-        self._fuse_norm_bwd = os.environ.get('MT_FUSE_NORM_BWD')
+        self._fuse_norm_bwd = None          # None: the default below; tests set 0 ... 3
         self._one_stream_at_init = self.bwdw_streams == 0       # (the default follows the stream setting the engine was built with)
         self.producer, self.pending = {}, {}
 
@@ -659,16 +652,10 @@ class Engine:
         self._io_cache = {}
         self._fp32_copies.clear()           # keyed by data_ptr: a re-planned buffer set may recycle an address with another shape / meaning
 
-    # ---- mixed precision: which level computes / stores what ------------------------------------------
-    def op_mma(self, out_spatial):
-        """matrix input type of a layer whose output has this spatial size"""
-        v = out_spatial[0] * out_spatial[1] * out_spatial[2]
-        return 1 if (self.mma and v >= self.bf16_min_voxels) else 0
-
+    # ---- mixed precision: what is stored as what --------------------------------------------------------
     def val_dtype(self, spatial):
         """storage type of an activation at this spatial size"""
-        v = spatial[0] * spatial[1] * spatial[2]
-        return self.act_storage if (self.mma and self.storage_bf16 and v >= self.bf16_min_voxels) else torch.float32
+        return torch.float16 if self.mma else torch.float32
 
     def grad_dtype(self, spatial):
         """storage type of the gradient of an activation at this spatial size"""
@@ -695,9 +682,6 @@ class Engine:
                     if supported(t.build()):
                         flags = cand
                         break
-                if os.environ.get('MT_IO_DEBUG') and flags != (False, False):
-                    print("[mt io] %s: %s copies (in %s, out %s)" % (key, 'input' if flags == (True, False) else 'output' if flags == (False, True) else 'input+output',
-                                                                     [str(a.dtype) for a in ins], [str(o.dtype) for o in outs]))
             self._io_cache[sig] = flags
         return _IO(self, key, ins, outs, build, flags, gi)
 
@@ -885,7 +869,7 @@ class Engine:
                 for r, f, o in zip(rec, is_fwd, owner):
                     if f:
                         acc += r[1].numel() * 4
-                        if acc > (2 << 20) and o > 0 and os.environ.get('MT_PACK_SPLIT', '1') != '0':
+                        if acc > (2 << 20) and o > 0:
                             mid_op = o
                             break
                 if mid_op is not None:

@@ -9,7 +9,6 @@ in numpy), and the final divide + threshold/argmax is one kernel.  Accumulation 
 With tile sharding (rank, world) each process handles a contiguous run of tiles, holds only the x range its tiles touch, owns
 one x-slab of the result and exchanges only the zones where neighbouring ranks' tiles overlap (point-to-point over RCCL) —
 functionality the reference does not have (it only strides CASES across processes, predict_MultiTalent.py:362)."""
-import os
 
 import numpy as np
 import torch
@@ -174,7 +173,7 @@ def predict_3D(net, x, do_mirroring, mirror_axes=(0, 1, 2), use_sliding_window=F
     # mixed_precision: the reference runs the forward passes under autocast (neural_network.py:136-137, its predict default) — here the
     # engine's mixed mode (fp16 activations and forward products); False = fp32, the parity path.  The engine is left as it was found.
     prev_mma = eng.mma
-    eng.set_precision('bf16' if (mixed_precision and os.environ.get('MT_INFER_MIXED', '1') != '0') else 'fp32')
+    eng.set_precision('bf16' if mixed_precision else 'fp32')
     was_training = net.training
     try:
         with torch.no_grad():
@@ -182,7 +181,7 @@ def predict_3D(net, x, do_mirroring, mirror_axes=(0, 1, 2), use_sliding_window=F
             # results do not depend on the batch, and the aggregate is still updated tile by tile in the reference's x -> y -> z
             # order with the reference's mirror order inside a tile): up to 8x larger grids on the low-resolution stages.  The
             # batch is cut out of the volume by ONE kernel with the flips folded into its index arithmetic (mt_extract_tiles).
-            fuse_head = num_classes <= 64 and os.environ.get('MT_INFER_FUSED_HEAD', '1') != '0'
+            fuse_head = num_classes <= 64
             for g0 in range(0, len(tiles), group):
                 chunk = tiles[g0:g0 + group]
                 desc = [(t, (0 in c, 1 in c, 2 in c)) for t in chunk for c in combos]

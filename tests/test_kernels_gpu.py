@@ -521,7 +521,7 @@ def test_conv_bf16_1x3x3(dev, N, Cin, Cout, shape):
     (30, 30, (3, 5, 20), True),       # odd H (half tile), channel tails
 ])
 def test_conv_bwd_weight_bf16_mixed_precision(dev, Cin, Cout, shape, lazy):
-    """mt_conv3d_t.mma = 1 with FP32 storage on both sides (the MT_BF16_STORAGE=0 experiment mode): since round 5 these launches take the
+    """mt_conv3d_t.mma = 1 with FP32 storage on both sides (what Engine.io's fp32-copy fallback launches): since round 5 these launches take the
     fp32 backward-weight kernels (the bf16 Winograd marching kernels are gone; 16-bit storage is served by conv_bwdw_tr16_kernel,
     tests/test_storage_bf16_gpu.py::test_bwdw_tr16_vs_host).  Against autograd, the accumulating form (dW += ...) on top."""
     ops = _ops()
