@@ -458,6 +458,41 @@ size_t mt_fill_holes3d_workspace(int D, int H, int W);
 int mt_fill_holes3d(uint8_t* mask, int D, int H, int W, int32_t* bbox, void* ws, size_t ws_bytes, mt_stream_t stream);
 int mt_crop_nonzero(const float* data, int C, int D, int H, int W, const uint8_t* mask, const int32_t* box /* host, 6 */, float* out,
                     const float* seg_in /* NULL or [CS][D, H, W] */, int CS, void* seg_out, float nonzero_label, mt_stream_t stream);
+/* Preprocessing a training case (preprocessing/preprocessing.py:273-353; preprocessing/device_preprocessing.py).  Additions to ABI 4.
+ * mt_masked_moments: for each of the C channels of the contiguous float32 data[C][V], over the voxels a predicate selects:
+ *   stats[c] (device doubles) = count, mean, population standard deviation (numpy's std, ddof 0).  Predicates: MT_MOMENTS_ALL,
+ *   MT_MOMENTS_SEG_GE0 (seg[v] >= 0, seg: float32 [V] shared by the channels), MT_MOMENTS_OPEN_RANGE (lo[c] < x < hi[c], HOST doubles,
+ *   compared in double).  Two passes in double (the mean, then the centred squares); per-block partials are combined in a fixed
+ *   order by a second small launch, no floating-point atomics: bit-identical from run to run.  An empty selection gives count 0 and
+ *   NaN for mean and sd.  At most 16 channels.  ws: mt_masked_moments_workspace(C, V) bytes of device scratch, 8-byte aligned.
+ * mt_intensity_normalize: in place on one channel x[V]:  x = clip(x, lo, hi) when clip != 0, then x = (x - m) / (s + eps) in float32
+ *   with a true division (numpy's arithmetic order), where (m, s) = (mean, sd), or (float)stats[1], (float)stats[2] of a device
+ *   triple that mt_masked_moments wrote when stats != NULL.  seg != NULL: voxels where seg[v] >= 0 does not hold become 0 (both masked
+ *   forms of the reference, `data[seg < 0] = 0` after normalising and `data[mask] = ...; data[mask == 0] = 0`, give this result).
+ * mt_label_counts / mt_label_locations: the class locations of _run_internal (:340-351).  seg: float32 label map [V]; a voxel belongs
+ *   to slot table[(int)seg[v]] when seg[v] is an integer in 0..L-1 and that entry is < nslots (table: L device bytes, 255 = no slot;
+ *   nslots <= 255).  mt_label_counts: counts[slot] (device int64) = number of voxels of the slot; it also leaves, in ws, the
+ *   exclusive offsets of every (slot, unit of MT_PP_UNIT consecutive voxels), which mt_label_locations needs: same seg, table, ws.
+ *   mt_label_locations: out[i] (device int64 [nq][3]) = the [x, y, z] coordinate in the [D, H, W] volume of the qrank[i]-th voxel
+ *   (C order, 0-based) of slot qslot[i], i.e. np.argwhere(seg == c)[rank]; a query outside the counts gives -1, -1, -1.  An ordered
+ *   compaction (unit counts, scan, int32 linear indices into idx, gather): the result does not depend on block scheduling.
+ *   idx: device int32 scratch of idx_capacity >= sum(counts) entries.  ws: mt_label_counts_workspace(V, nslots) bytes, 8-byte
+ *   aligned.  V > INT32_MAX is MT_EINVAL before any launch. */
+#define MT_MOMENTS_ALL 0
+#define MT_MOMENTS_SEG_GE0 1
+#define MT_MOMENTS_OPEN_RANGE 2
+#define MT_PP_UNIT 8192
+size_t mt_masked_moments_workspace(int C, long V);
+int mt_masked_moments(const float* data, int C, long V, int pred, const float* seg, const double* lo /* host, C */,
+                      const double* hi /* host, C */, double* stats, void* ws, size_t ws_bytes, mt_stream_t stream);
+int mt_intensity_normalize(float* x, long V, int clip, float lo, float hi, float mean, float sd, const double* stats, float eps,
+                           const float* seg, mt_stream_t stream);
+size_t mt_label_counts_workspace(long V, int nslots);
+int mt_label_counts(const float* seg, long V, const uint8_t* table, int L, int nslots, int64_t* counts, void* ws, size_t ws_bytes,
+                    mt_stream_t stream);
+int mt_label_locations(const float* seg, int D, int H, int W, const uint8_t* table, int L, int nslots, void* ws, size_t ws_bytes,
+                       int32_t* idx, long idx_capacity, const int32_t* qslot, const int64_t* qrank, long nq, int64_t* out,
+                       mt_stream_t stream);
 /* Evaluation (evaluation/evaluator.py, evaluation/metrics.py:314-383).
  * mt_seg_joint_hist: one pass over two contiguous uint8 label volumes of V voxels (any alignment; V is not limited to int32):
  *   hist[remap[test[v]] * C + remap[ref[v]]] += 1, exact 64-bit counts in the device array hist[C * C] (zeroed by the call).

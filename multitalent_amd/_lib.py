@@ -128,6 +128,12 @@ SIGNATURES = {
     'mt_fill_holes3d_workspace': (_sz, [_i, _i, _i]),
     'mt_fill_holes3d': (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'mt_crop_nonzero': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp]),
+    'mt_masked_moments_workspace': (_sz, [_i, _l]),
+    'mt_masked_moments': (_i, [_vp, _i, _l, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'mt_intensity_normalize': (_i, [_vp, _l, _i, _f, _f, _f, _f, _vp, _f, _vp, _vp]),
+    'mt_label_counts_workspace': (_sz, [_l, _i]),
+    'mt_label_counts': (_i, [_vp, _l, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    'mt_label_locations': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp, _l, _vp, _vp, _l, _vp, _vp]),
     'mt_seg_joint_hist': (_i, [_vp, _vp, _l, _vp, _i, _vp, _vp]),
     'mt_surface_distances_workspace': (_sz, [_i, _i, _i, _l]),
     'mt_surface_distances': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _l, _vp, _vp, _sz, _vp]),

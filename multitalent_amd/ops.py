@@ -807,6 +807,132 @@ def crop_nonzero(data, mask, box, seg=None, nonzero_label=-1):
     return out, seg_out
 
 
+MOMENTS_ALL, MOMENTS_SEG_GE0, MOMENTS_OPEN_RANGE = 0, 1, 2
+MOMENTS_MAX_CHANNELS = 16
+LABEL_MAX_VOXELS = CC_MAX_VOXELS  # mt_label_counts / mt_label_locations: int32 linear indices
+LABEL_MAX_CLASSES = 255
+
+
+def _check_pre_dev(*ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("multitalent_amd: training-case preprocessing runs on a HIP device only; there is no CPU fallback")
+
+
+def masked_moments(data, pred=MOMENTS_ALL, seg=None, lo=None, hi=None, stats=None):
+    """data: [C, ...] float32 device tensor (contiguous).  -> stats, float64 device tensor [C, 3] = count, mean, population sd of
+    every channel over the voxels the predicate selects: all of them, those with seg >= 0 (seg: float32, data.shape[1:]), or those
+    with lo[c] < x < hi[c] (host values); see mt_masked_moments.  Deterministic; nothing is synchronised."""
+    _check_pre_dev(data)
+    assert data.dtype == torch.float32 and data.is_contiguous() and data.dim() >= 2
+    Cn = int(data.shape[0])
+    V = int(data.numel()) // max(Cn, 1)
+    if not 1 <= Cn <= MOMENTS_MAX_CHANNELS or V < 1:
+        raise ValueError("masked_moments: 1..%d non-empty channels are expected, got shape %s" % (MOMENTS_MAX_CHANNELS, tuple(data.shape)))
+    seg_ptr = lo_ptr = hi_ptr = None
+    if pred == MOMENTS_SEG_GE0:
+        _check_pre_dev(seg)
+        assert seg.dtype == torch.float32 and seg.is_contiguous() and seg.numel() == V
+        seg_ptr = _ptr(seg)
+    elif pred == MOMENTS_OPEN_RANGE:
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (Cn,)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (Cn,)))
+        lo_ptr, hi_ptr = lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p)
+    elif pred != MOMENTS_ALL:
+        raise ValueError("masked_moments: unknown predicate %r" % (pred,))
+    lib = _lib.load()
+    ws = torch.empty(int(lib.mt_masked_moments_workspace(Cn, V)), dtype=torch.uint8, device=data.device)
+    if stats is None:
+        stats = torch.empty((Cn, 3), dtype=torch.float64, device=data.device)
+    _check_pre_dev(stats)
+    assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == Cn * 3
+    _lib.check(lib.mt_masked_moments(_ptr(data), Cn, V, int(pred), seg_ptr, lo_ptr, hi_ptr, _ptr(stats), _ptr(ws), ws.numel(), _stream()),
+               'masked_moments')
+    return stats
+
+
+def intensity_normalize(x, clip=None, mean=0.0, sd=1.0, stats=None, eps=0.0, seg=None):
+    """In place on one channel x (float32 device tensor, contiguous): clip to `clip` = (lo, hi) when given, then
+    (x - m) / (s + eps) in float32 with (m, s) = (mean, sd), or the (mean, sd) of `stats` (one float64 device triple of
+    masked_moments); where `seg` (float32, same size) is not >= 0 the result is 0.  See mt_intensity_normalize."""
+    _check_pre_dev(x)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0
+    seg_ptr = stats_ptr = None
+    if seg is not None:
+        _check_pre_dev(seg)
+        assert seg.dtype == torch.float32 and seg.is_contiguous() and seg.numel() == x.numel()
+        seg_ptr = _ptr(seg)
+    if stats is not None:
+        _check_pre_dev(stats)
+        assert stats.dtype == torch.float64 and stats.numel() == 3 and stats.is_contiguous()
+        stats_ptr = _ptr(stats)
+    lo, hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
+    _lib.check(_lib.load().mt_intensity_normalize(_ptr(x), x.numel(), 0 if clip is None else 1, lo, hi, float(mean), float(sd), stats_ptr,
+                                                  float(eps), seg_ptr, _stream()), 'intensity_normalize')
+    return x
+
+
+class LabelIndex:
+    """State between label_counts and label_locations: the label map, the label-to-slot table and the unit offsets."""
+
+    def __init__(self, seg, table, nslots, counts, ws):
+        self.seg, self.table, self.nslots, self.counts, self.ws = seg, table, nslots, counts, ws
+
+
+def label_counts(seg, all_classes):
+    """seg: [D, H, W] float32 label map (contiguous device tensor); all_classes: up to 255 distinct non-negative integer labels.
+    -> (counts, index): counts[i] (int64 device tensor) = number of voxels with label all_classes[i]; `index` goes to
+    label_locations.  See mt_label_counts.  Nothing is synchronised."""
+    shape = tuple(int(i) for i in seg.shape)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError("label_counts: a non-empty 3-D label map [D, H, W] is expected, got shape %s" % (shape,))
+    if shape[0] * shape[1] * shape[2] > LABEL_MAX_VOXELS:
+        raise ValueError("label_counts: %d voxels exceed the int32 index range of the device compaction" % (shape[0] * shape[1] * shape[2]))
+    classes = [int(c) for c in all_classes]
+    if not 1 <= len(classes) <= LABEL_MAX_CLASSES or min(classes) < 0 or len(set(classes)) != len(classes):
+        raise ValueError("label_counts: 1..%d distinct non-negative labels are expected, got %s" % (LABEL_MAX_CLASSES, classes))
+    if any(c != f for c, f in zip(classes, all_classes)):
+        raise ValueError("label_counts: labels must be integers, got %s" % (list(all_classes),))
+    _check_pre_dev(seg)
+    assert seg.dtype == torch.float32 and seg.is_contiguous()
+    tab = np.full(max(classes) + 1, 255, dtype=np.uint8)
+    tab[classes] = np.arange(len(classes), dtype=np.uint8)
+    table = torch.from_numpy(tab).to(seg.device)
+    lib = _lib.load()
+    V = seg.numel()
+    ws = torch.empty(int(lib.mt_label_counts_workspace(V, len(classes))), dtype=torch.uint8, device=seg.device)
+    counts = torch.empty(len(classes), dtype=torch.int64, device=seg.device)
+    _lib.check(lib.mt_label_counts(_ptr(seg), V, _ptr(table), table.numel(), len(classes), _ptr(counts), _ptr(ws), ws.numel(), _stream()),
+               'label_counts')
+    return counts, LabelIndex(seg, table, len(classes), counts, ws)
+
+
+def label_locations(index, qslot, qrank, total=None):
+    """index: from label_counts; qslot / qrank: equally long host or device integer arrays, query i asks for the qrank[i]-th voxel
+    (C order) with label all_classes[qslot[i]].  -> int64 device tensor [n, 3] of coordinates = np.argwhere(seg == c)[rank]
+    (-1 for a rank outside the count).  total: sum of the counts when the caller already has it on the host (sizes the scratch);
+    otherwise it is read back here."""
+    seg = index.seg
+    qslot = torch.as_tensor(np.asarray(qslot) if not torch.is_tensor(qslot) else qslot).to(device=seg.device, dtype=torch.int32).contiguous()
+    qrank = torch.as_tensor(np.asarray(qrank) if not torch.is_tensor(qrank) else qrank).to(device=seg.device, dtype=torch.int64).contiguous()
+    assert qslot.dim() == 1 and qslot.shape == qrank.shape
+    n = int(qslot.numel())
+    out = torch.empty((n, 3), dtype=torch.int64, device=seg.device)
+    if n == 0:
+        return out
+    if total is None:
+        total = int(index.counts.sum().item())
+    total = int(total)
+    if total < 1:
+        return out.fill_(-1)
+    idx = torch.empty(total, dtype=torch.int32, device=seg.device)
+    D, H, W = (int(i) for i in seg.shape)
+    _lib.check(_lib.load().mt_label_locations(_ptr(seg), D, H, W, _ptr(index.table), index.table.numel(), index.nslots, _ptr(index.ws),
+                                              index.ws.numel(), _ptr(idx), total, _ptr(qslot), _ptr(qrank), n, _ptr(out), _stream()),
+               'label_locations')
+    return out
+
+
 SD_MAX_AXIS = 32766             # mt_surface_distances: int16 site offsets
 SELECT_MAX_RANKS = 8
 

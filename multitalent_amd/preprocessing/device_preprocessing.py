@@ -1,16 +1,22 @@
-"""Inference pre-processing on the device (first half): resampling a cropped CT volume to the plan's spacing and
-the CT intensity normalisation — GenericPreprocessor.resample_and_normalize (preprocessing.py:226-311) with resample_patient /
-resample_data_or_seg(is_seg=False, order 3, separate z with order 0) (preprocessing.py:38-197).
+"""Pre-processing on the device: resampling a cropped volume and its label map to the plan's spacing, the
+intensity normalisation schemes and the sampled class locations — GenericPreprocessor.resample_and_normalize and _run_internal
+(preprocessing.py:226-353) with resample_patient / resample_data_or_seg (preprocessing.py:38-197).
 
-skimage.transform.resize(order=3, mode='edge', anti_aliasing=False) is scipy.ndimage.zoom(order=3, mode='nearest',
-grid_mode=True): the volume is edge-padded by 12 voxels, spline-prefiltered and sampled at x = (o + 0.5) * in/out - 0.5.  Here:
-replicate padding (torch glue), `mt_spline_prefilter3`, `mt_affine_sample` (cubic, diagonal matrix).  The prefilter initialises
-with mirror boundaries where scipy uses its 'nearest' rule; twelve voxels of edge padding damp the difference to z^12 = 1.4e-7.
+Data (order 3, separate z with order 0): skimage.transform.resize(order=3, mode='edge', anti_aliasing=False) is
+scipy.ndimage.zoom(order=3, mode='nearest', grid_mode=True): the volume is edge-padded by 12 voxels, spline-prefiltered and
+sampled at x = (o + 0.5) * in/out - 0.5.  Here: replicate padding (torch glue), `mt_spline_prefilter3`, `mt_affine_sample` (cubic,
+diagonal matrix).  The prefilter initialises with mirror boundaries where scipy uses its 'nearest' rule; twelve voxels of edge
+padding damp the difference to z^12 = 1.4e-7.
+Labels (order 1, separate z with order 0): batchgenerators' resize_segmentation — per label the order-1 resize of its indicator,
+ascending labels overwrite where it reaches 0.5 — is `mt_affine_sample` mode 11 on a volume edge-padded by one voxel.
+Normalisation: `mt_masked_moments` (per-case mean / sd in double) and `mt_intensity_normalize` (one fused in-place pass).
+Class locations: `mt_label_counts` / `mt_label_locations`; the host draws the reference's random ranks, the device resolves them.
 The crop to the non-zero region in front of this is `device_cropping.py` (also on the device); file I/O stays with the caller."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .. import ops
 from ..inference.segmentation_export import get_do_separate_z, get_lowres_axis
 from ..training.data_augmentation.spatial import affine_sample
 
@@ -53,18 +59,9 @@ def resample_data(data, new_shape, axis=None, do_separate_z=False):
     return out.permute(inv).contiguous()
 
 
-def resample_and_normalize_ct(data, original_spacing, target_spacing, intensityproperties, force_separate_z=None,
-                              separate_z_anisotropy_threshold=3):
-    """data: [C, X, Y, Z] (already cropped and transposed) numpy or device tensor; every modality is normalised with the "CT"
-    scheme (clip to the training set's 0.5 / 99.5 percentiles, subtract its mean, divide by its sd).  Returns a device tensor."""
-    if not torch.is_tensor(data):
-        data = torch.from_numpy(np.ascontiguousarray(data))
-    if not data.is_cuda:
-        if not torch.cuda.is_available():
-            raise RuntimeError("multitalent_amd: device pre-processing runs on a HIP device only; there is no CPU fallback")
-        data = data.cuda()
-    data = torch.nan_to_num(data.float(), nan=0.0, posinf=None, neginf=None) if torch.isnan(data).any() else data.float()
-    shape = np.array(data.shape[1:])
+def resampling_plan(shape, original_spacing, target_spacing, force_separate_z=None, separate_z_anisotropy_threshold=3):
+    """resample_patient's decisions (preprocessing.py:67-95): -> (new_shape, do_separate_z, axis)."""
+    shape = np.array(shape)
     new_shape = np.round(((np.array(original_spacing) / np.array(target_spacing)).astype(float) * shape)).astype(int)
     if force_separate_z is not None:
         sep, axis = force_separate_z, (get_lowres_axis(original_spacing) if force_separate_z else None)
@@ -76,6 +73,27 @@ def resample_and_normalize_ct(data, original_spacing, target_spacing, intensityp
         sep, axis = False, None
     if axis is not None and len(axis) != 1:
         sep = False
+    return new_shape, sep, axis
+
+
+def _to_device(x):
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not x.is_cuda:
+        if not torch.cuda.is_available():
+            raise RuntimeError("multitalent_amd: device pre-processing runs on a HIP device only; there is no CPU fallback")
+        x = x.cuda()
+    return x
+
+
+def resample_and_normalize_ct(data, original_spacing, target_spacing, intensityproperties, force_separate_z=None,
+                              separate_z_anisotropy_threshold=3):
+    """data: [C, X, Y, Z] (already cropped and transposed) numpy or device tensor; every modality is normalised with the "CT"
+    scheme (clip to the training set's 0.5 / 99.5 percentiles, subtract its mean, divide by its sd).  Returns a device tensor."""
+    data = _to_device(data)
+    data = torch.nan_to_num(data.float(), nan=0.0, posinf=None, neginf=None) if torch.isnan(data).any() else data.float()
+    new_shape, sep, axis = resampling_plan(data.shape[1:], original_spacing, target_spacing, force_separate_z,
+                                           separate_z_anisotropy_threshold)
     out = resample_data(data, new_shape, axis, sep)
     if out is data:
         out = data.clone()
@@ -83,3 +101,120 @@ def resample_and_normalize_ct(data, original_spacing, target_spacing, intensityp
         ip = intensityproperties[c]
         out[c].clamp_(float(ip['percentile_00_5']), float(ip['percentile_99_5'])).sub_(float(ip['mean'])).div_(float(ip['sd']))
     return out
+
+
+def _zoom_seg(x, new_shape, planar):
+    """x: [1, C, D, H, W] label maps -> [1, C, *new_shape] by the per-label order-1 rule; one voxel of edge padding keeps every
+    sampling coordinate (o + 0.5) * in/out - 0.5 >= -0.5 inside the padded volume (the reference's mode='edge')."""
+    D, H, W = (int(i) for i in x.shape[2:])
+    xp = F.pad(x, (1, 1, 1, 1, 0, 0) if planar else (1,) * 6, mode='replicate')
+    m = np.zeros((1, 12), dtype=np.float32)
+    m[0, 0], m[0, 4], m[0, 8] = 1.0 if planar else D / new_shape[0], H / new_shape[1], W / new_shape[2]
+    m[0, 9:] = [0 if planar else D / 2. - 0.5 + 1, H / 2. - 0.5 + 1, W / 2. - 0.5 + 1]
+    return affine_sample(xp, m, tuple(int(i) for i in new_shape), 1, cval=0.0, is_seg=True, planar=planar)
+
+
+def resample_seg(seg, new_shape, axis=None, do_separate_z=False):
+    """resample_data_or_seg(seg, new_shape, is_seg=True, axis, order=1, do_separate_z, order_z=0) for a [C, X, Y, Z] label map:
+    result 0, then the labels in ascending order overwrite where the order-1 interpolation of their indicator is >= 0.5 (so -1
+    stays only where no label >= 0 reaches 0.5); with separate z that rule per slice, then order 0 along the anisotropic axis."""
+    if not seg.is_cuda:
+        raise RuntimeError("multitalent_amd: device pre-processing runs on a HIP device only; there is no CPU fallback")
+    assert seg.dim() == 4
+    shape = tuple(int(i) for i in seg.shape[1:])
+    new_shape = tuple(int(i) for i in new_shape)
+    if shape == new_shape:
+        return seg
+    x = seg.float()
+    if not do_separate_z:
+        return _zoom_seg(x[None].contiguous(), new_shape, planar=False)[0]
+    assert len(axis) == 1, "only one anisotropic axis supported"
+    ax = int(axis[0])
+    perm = [0, 1 + ax] + [1 + i for i in range(3) if i != ax]
+    inv = [perm.index(i) for i in range(4)]
+    xs = x.permute(perm).contiguous()
+    ns = [new_shape[ax]] + [new_shape[i] for i in range(3) if i != ax]
+    out = xs if tuple(xs.shape[2:]) == (ns[1], ns[2]) else _zoom_seg(xs[None], (xs.shape[1], ns[1], ns[2]), planar=True)[0]
+    if xs.shape[1] != ns[0]:
+        o = torch.arange(ns[0], device=x.device, dtype=torch.float64)
+        idx = torch.floor((o + 0.5) * (xs.shape[1] / ns[0]) - 0.5 + 0.5).clamp_(0, xs.shape[1] - 1).long()
+        out = out.index_select(1, idx)
+    return out.permute(inv).contiguous()
+
+
+def normalize(data, seg, schemes, use_mask, intensityproperties):
+    """The normalisation loop of resample_and_normalize (preprocessing.py:273-310), in place on the [C, X, Y, Z] float32 device
+    tensor `data`; seg: [Cs, X, Y, Z] float32 (its last channel carries the -1 of the non-zero mask) or None when no modality uses
+    the mask.  schemes / use_mask: per modality.  The per-case means and sds are formed in double on the device (the reference
+    takes them in float32) and never visit the host."""
+    assert data.is_cuda and data.dtype == torch.float32 and data.is_contiguous() and data.dim() == 4
+    assert len(schemes) == len(data), "self.normalization_scheme_per_modality must have as many entries as data has modalities"
+    assert len(use_mask) == len(data), "self.use_nonzero_mask must have as many entries as data has modalities"
+    m = None
+    if any(use_mask):
+        assert seg is not None, "use_mask_for_norm needs the segmentation (its -1 marks the region outside the non-zero mask)"
+        m = seg[-1].float().contiguous()
+        assert tuple(m.shape) == tuple(data.shape[1:])
+    for c, scheme in enumerate(schemes):
+        mc = m if use_mask[c] else None
+        if scheme in ("CT", "CT2"):
+            assert intensityproperties is not None, "ERROR: if there is a CT then we need intensity properties"
+            ip = intensityproperties[c]
+            lo, hi = float(ip['percentile_00_5']), float(ip['percentile_99_5'])
+            if scheme == "CT":
+                ops.intensity_normalize(data[c], (lo, hi), float(ip['mean']), float(ip['sd']), seg=mc)
+            else:
+                st = ops.masked_moments(data[c:c + 1], ops.MOMENTS_OPEN_RANGE, lo=[lo], hi=[hi])
+                ops.intensity_normalize(data[c], (lo, hi), stats=st[0], seg=mc)
+        elif scheme == 'noNorm':
+            pass
+        elif mc is not None:
+            st = ops.masked_moments(data[c:c + 1], ops.MOMENTS_SEG_GE0, seg=mc)
+            ops.intensity_normalize(data[c], stats=st[0], eps=1e-8, seg=mc)
+        else:
+            st = ops.masked_moments(data[c:c + 1], ops.MOMENTS_ALL)
+            ops.intensity_normalize(data[c], stats=st[0], eps=1e-8)
+    return data
+
+
+NUM_LOCATION_SAMPLES = 10000
+MIN_PERCENT_COVERAGE = 0.01
+
+
+def draw_class_ranks(counts, seed=1234):
+    """The random stream of _run_internal (preprocessing.py:338-351) on the voxel counts alone: one RandomState(seed) per case,
+    classes visited in order, an empty class draws nothing.  -> per class the drawn ranks into np.argwhere(seg == c), or None."""
+    rndst = np.random.RandomState(seed)
+    ranks = []
+    for n in counts:
+        n = int(n)
+        if n == 0:
+            ranks.append(None)
+            continue
+        k = max(min(NUM_LOCATION_SAMPLES, n), int(np.ceil(n * MIN_PERCENT_COVERAGE)))
+        ranks.append(rndst.choice(n, k, replace=False))
+    return ranks
+
+
+def class_locations(seg, all_classes):
+    """properties['class_locations'] of _run_internal for the [X, Y, Z] float32 device label map `seg`: {c: int64 [k, 3] numpy array
+    of sampled voxel coordinates, or [] for a class without voxels}, element for element the reference's.  The counts come back
+    from the device, the host draws the ranks, the device resolves them to coordinates."""
+    all_classes = list(all_classes)
+    if len(all_classes) == 0:
+        return {}
+    counts_dev, index = ops.label_counts(seg.contiguous(), all_classes)
+    counts = counts_dev.cpu().numpy()
+    ranks = draw_class_ranks(counts)
+    drawn = [(i, r) for i, r in enumerate(ranks) if r is not None]
+    locs = {}
+    if drawn:
+        qslot = np.concatenate([np.full(len(r), i, dtype=np.int32) for i, r in drawn])
+        qrank = np.concatenate([r.astype(np.int64) for _, r in drawn])
+        out = ops.label_locations(index, qslot, qrank, total=int(counts.sum())).cpu().numpy()
+        assert out.min() >= 0, "class_locations: a rank fell outside its class (counts and label map disagree)"
+        pos = 0
+        for i, r in drawn:
+            locs[i] = out[pos:pos + len(r)]
+            pos += len(r)
+    return {c: (locs[i] if i in locs else []) for i, c in enumerate(all_classes)}
