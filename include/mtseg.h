@@ -522,6 +522,35 @@ int mt_surface_distances(const uint8_t* test, const uint8_t* ref, int D, int H, 
                          int connectivity, double* out, long capacity, double* stats, void* ws, size_t ws_bytes, mt_stream_t stream);
 size_t mt_select_kth_workspace(int nranks);
 int mt_select_kth(const double* x, long n, const long* ranks, int nranks, double* out, void* ws, size_t ws_bytes, mt_stream_t stream);
+/* The dataset fingerprint (experiment_planning/DatasetAnalyzer.py:161-224; multitalent_amd/experiment_planning/DatasetAnalyzer.py) and
+ * the np.unique of a label map (preprocessing/cropping.py:146, DatasetAnalyzer.py:83).  Additions to ABI 4.
+ * mt_fg_sample_count / mt_fg_sample_gather: data[c][seg > 0][::stride] for the C channels of the contiguous float32 data[C][V] at once.
+ *   The selection is the voxels with seg[v] > 0 (seg: float32 [V]; a float comparison: -1, 0 and NaN are not selected); n = their
+ *   number, m = ceil(n / stride).  mt_fg_sample_count: *count (device int64) = n; it also leaves, in ws, the exclusive offset of
+ *   every unit of MT_PP_UNIT consecutive voxels, which mt_fg_sample_gather needs: same seg, ws.  mt_fg_sample_gather:
+ *   out[c * out_cs + j] = data[c][v_(j * stride)] for j < m, where v_r is the r-th selected voxel in C order: bit for bit, NaN
+ *   payloads included; nan_counts[c] (device int64) = the number of NaNs among channel c's m samples.  out_cs >= m is the channel
+ *   stride of out (a case can be written into its slot of a larger buffer); samples at or beyond out_cs are dropped.  An ordered
+ *   compaction (unit counts, scan, ballot ranks) with integer arithmetic only: the result does not depend on block scheduling.
+ *   ws: mt_fg_sample_workspace(V) bytes of device scratch, 8-byte aligned.  V > INT32_MAX, C > 16 or stride < 1 is MT_EINVAL, too
+ *   small a workspace MT_EWORKSPACE, both before any launch.
+ * mt_select_kth_f32: out[r] (device float32) = the ranks[r]-th smallest (0-based) of the n float32 values x (4-byte aligned; n may
+ *   exceed 2^32), for nranks <= 8 HOST ranks: radix select, 4 passes of 8 bits, on the key bits ^ (sign ? 0xffffffff : 0x80000000).
+ *   The result is an element of x: -0.0 orders before +0.0, +-inf and denormals order as numbers, NaNs by bit pattern (the result
+ *   is then unspecified).  All ranks share each pass over x; integer histograms: bit-identical from run to run.
+ *   ws: mt_select_kth_f32_workspace(nranks) bytes of device scratch, 8-byte aligned.  n < 1, a rank outside 0..n-1 or nranks
+ *   outside 1..8 is MT_EINVAL, too small a workspace MT_EWORKSPACE, both before any launch.
+ * mt_label_presence: one pass over the float32 label map seg[V] (any V): bit (l + 1) % 32 of bitmap[(l + 1) / 32] (device uint32[32])
+ *   is set exactly when some voxel equals the integer l in -1..1022; *flag (device int32) = 1 when any voxel is non-integral, NaN or
+ *   outside that range, else 0.  Both are written by the call (no need to clear them). */
+size_t mt_fg_sample_workspace(long V);
+int mt_fg_sample_count(const float* seg, long V, int64_t* count, void* ws, size_t ws_bytes, mt_stream_t stream);
+int mt_fg_sample_gather(const float* data, int C, long V, const float* seg, long stride, const void* ws, size_t ws_bytes, float* out,
+                        long out_cs, int64_t* nan_counts, mt_stream_t stream);
+size_t mt_select_kth_f32_workspace(int nranks);
+int mt_select_kth_f32(const float* x, long n, const long* ranks /* host */, int nranks, float* out, void* ws, size_t ws_bytes,
+                      mt_stream_t stream);
+int mt_label_presence(const float* seg, long V, uint32_t* bitmap, int32_t* flag, mt_stream_t stream);
 /* ---- device-side target preparation ----------------------------------------
  * Deep-supervision label pyramid: DownsampleSegForDSTransform2 / downsample_seg_for_ds_transform2 (downsampling.py:70-104,
  * order 0 = nearest through batchgenerators' resize_segmentation -> skimage.transform.resize(order 0, mode "edge") ->

@@ -139,6 +139,12 @@ SIGNATURES = {
     'mt_surface_distances': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _l, _vp, _vp, _sz, _vp]),
     'mt_select_kth_workspace': (_sz, [_i]),
     'mt_select_kth': (_i, [_vp, _l, _vp, _i, _vp, _vp, _sz, _vp]),
+    'mt_fg_sample_workspace': (_sz, [_l]),
+    'mt_fg_sample_count': (_i, [_vp, _l, _vp, _vp, _sz, _vp]),
+    'mt_fg_sample_gather': (_i, [_vp, _i, _l, _vp, _l, _vp, _sz, _vp, _l, _vp, _vp]),
+    'mt_select_kth_f32_workspace': (_sz, [_i]),
+    'mt_select_kth_f32': (_i, [_vp, _l, _vp, _i, _vp, _vp, _sz, _vp]),
+    'mt_label_presence': (_i, [_vp, _l, _vp, _vp, _vp]),
     'mt_head_flip_accumulate': (_i, [_P(mt_pointwise_t), _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
     'mt_head_mirror_accumulate': (_i, [_P(mt_pointwise_t), _i, _i, _vp, _i, _f, _vp, _vp, _vp, _l, _l, _l, _i, _i, _i, _vp]),
     'mt_extract_tiles': (_i, [_vp, _i, _l, _l, _l, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -1048,5 +1048,137 @@ def select_kth(x, ranks, out=None, ws=None):
     return out
 
 
+FG_MAX_VOXELS = CC_MAX_VOXELS     # mt_fg_sample_count / mt_fg_sample_gather: int32 ranks
+FG_MAX_CHANNELS = 16
+LABEL_PRESENCE_MIN, LABEL_PRESENCE_MAX = -1, 1022
+
+
+def _check_an_dev(*ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("multitalent_amd: the dataset analysis kernels run on a HIP device only; there is no CPU fallback")
+
+
+class FgIndex:
+    """State between fg_sample_count and fg_sample: the label map, the unit offsets and the foreground count."""
+
+    def __init__(self, seg, ws, count):
+        self.seg, self.ws, self.count, self._n = seg, ws, count, None
+
+    @property
+    def n(self):
+        """The number of voxels with seg > 0 as a host int (the one read-back, made on first use)."""
+        if self._n is None:
+            self._n = int(self.count.item())
+        return self._n
+
+
+def fg_sample_count(seg):
+    """seg: contiguous float32 device tensor (a label map, any shape).  -> FgIndex: `.count` (int64 device tensor [1]) = number of
+    voxels with seg > 0, `.n` the same on the host; it goes to fg_sample.  See mt_fg_sample_count.  Nothing is synchronised here."""
+    V = int(seg.numel())
+    if V < 1:
+        raise ValueError("fg_sample_count: an empty label map")
+    if V > FG_MAX_VOXELS:
+        raise ValueError("fg_sample_count: %d voxels exceed the int32 index range of the device compaction" % V)
+    _check_an_dev(seg)
+    assert seg.dtype == torch.float32 and seg.is_contiguous()
+    lib = _lib.load()
+    ws = torch.empty(int(lib.mt_fg_sample_workspace(V)), dtype=torch.uint8, device=seg.device)
+    count = torch.empty(1, dtype=torch.int64, device=seg.device)
+    _lib.check(lib.mt_fg_sample_count(_ptr(seg), V, _ptr(count), _ptr(ws), ws.numel(), _stream()), 'fg_sample_count')
+    return FgIndex(seg, ws, count)
+
+
+def fg_sample(data, seg, stride=10, out=None, offset=0, index=None):
+    """data: [C, ...] float32 device tensor (contiguous, 1..16 channels), seg: float32 label map with data.shape[1:] voxels.
+    -> (samples, n, nan_counts): samples [C, m] = data[c][seg > 0][::stride] bit for bit, m = ceil(n / stride); n the number of
+    foreground voxels (host int: the one read-back); nan_counts, int64 device tensor [C], the NaNs among each channel's samples.
+    out: a float32 device tensor [C, capacity]: the samples go to out[:, offset:offset + m], of which `samples` is then a view.
+    index: the FgIndex of fg_sample_count(seg) when the caller made that call already (to size `out`).  See mt_fg_sample_gather."""
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("fg_sample: stride %d < 1" % stride)
+    if data.dim() < 2:
+        raise ValueError("fg_sample: data [C, ...] is expected, got shape %s" % (tuple(data.shape),))
+    Cn = int(data.shape[0])
+    V = int(seg.numel())
+    if not 1 <= Cn <= FG_MAX_CHANNELS:
+        raise ValueError("fg_sample: %d channels (1..%d)" % (Cn, FG_MAX_CHANNELS))
+    if V < 1 or int(data.numel()) != Cn * V:
+        raise ValueError("fg_sample: data %s and seg %s do not match" % (tuple(data.shape), tuple(seg.shape)))
+    _check_an_dev(data, seg)
+    assert data.dtype == torch.float32 and data.is_contiguous()
+    if index is None:
+        index = fg_sample_count(seg)
+    elif index.seg is not seg and (index.seg.data_ptr() != seg.data_ptr() or index.seg.numel() != V):
+        raise ValueError("fg_sample: the index belongs to another label map")
+    n = index.n
+    m = (n + stride - 1) // stride
+    offset = int(offset)
+    if out is None:
+        if offset != 0:
+            raise ValueError("fg_sample: an offset needs `out`")
+        out = torch.empty((Cn, m), dtype=torch.float32, device=data.device)
+    _check_an_dev(out)
+    if out.dim() != 2 or int(out.shape[0]) != Cn or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("fg_sample: out must be a contiguous float32 tensor [%d, capacity]" % Cn)
+    cap = int(out.shape[1])
+    if offset < 0 or offset + m > cap:
+        raise ValueError("fg_sample: %d samples at offset %d do not fit the capacity %d" % (m, offset, cap))
+    nan_counts = torch.zeros(Cn, dtype=torch.int64, device=data.device)
+    if m > 0:
+        lib = _lib.load()
+        _lib.check(lib.mt_fg_sample_gather(_ptr(data), Cn, V, _ptr(seg), stride, _ptr(index.ws), index.ws.numel(),
+                                           C.c_void_p(out.data_ptr() + 4 * offset), cap, _ptr(nan_counts), _stream()), 'fg_sample_gather')
+    return out[:, offset:offset + m], n, nan_counts
+
+
+def select_kth_f32(x, ranks, out=None, ws=None):
+    """x: 1-D contiguous float32 device tensor (any 4-byte aligned view); ranks: up to 8 host ints in 0..len(x)-1.
+    -> float32 device tensor [len(ranks)]: the ranks[r]-th smallest of x, an element of x (radix select on signed floats, see
+    mt_select_kth_f32).  Nothing is synchronised."""
+    ranks = [int(r) for r in ranks]
+    n = int(x.numel())
+    if x.dim() != 1 or n < 1:
+        raise ValueError("select_kth_f32: a non-empty 1-D tensor is expected, got shape %s" % (tuple(x.shape),))
+    if not 1 <= len(ranks) <= SELECT_MAX_RANKS:
+        raise ValueError("select_kth_f32: %d ranks (1..%d)" % (len(ranks), SELECT_MAX_RANKS))
+    if min(ranks) < 0 or max(ranks) >= n:
+        raise ValueError("select_kth_f32: ranks %s outside 0..%d" % (ranks, n - 1))
+    _check_an_dev(x)
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(len(ranks), dtype=torch.float32, device=x.device)
+    if ws is None:
+        ws = torch.empty(lib.mt_select_kth_f32_workspace(len(ranks)), dtype=torch.uint8, device=x.device)
+    _check_an_dev(out, ws)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= len(ranks)
+    rk = (C.c_long * len(ranks))(*ranks)
+    _lib.check(lib.mt_select_kth_f32(_ptr(x), n, C.cast(rk, C.c_void_p), len(ranks), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+               'select_kth_f32')
+    return out
+
+
+def label_presence(seg, what='label map'):
+    """seg: contiguous float32 device tensor holding integer labels in -1..1022.  -> sorted list of the labels that occur
+    (np.unique(seg) as Python ints; one read-back of 33 words).  A non-integral value, a NaN or a label outside the range raises
+    ValueError naming `what` (the case).  See mt_label_presence."""
+    V = int(seg.numel())
+    if V < 1:
+        raise ValueError("label_presence: %s is empty" % what)
+    _check_an_dev(seg)
+    assert seg.dtype == torch.float32 and seg.is_contiguous()
+    buf = torch.empty(33, dtype=torch.int32, device=seg.device)
+    _lib.check(_lib.load().mt_label_presence(_ptr(seg), V, _ptr(buf), C.c_void_p(buf.data_ptr() + 4 * 32), _stream()), 'label_presence')
+    host = buf.cpu().numpy()
+    if host[32] != 0:
+        raise ValueError("label_presence: %s holds a value that is not an integer label in %d..%d (a fraction, a NaN or a label "
+                         "outside the range); there is no host fallback" % (what, LABEL_PRESENCE_MIN, LABEL_PRESENCE_MAX))
+    bits = np.unpackbits(host[:32].view(np.uint8), bitorder='little')
+    return [int(b) - 1 for b in np.flatnonzero(bits)]
+
+
 _parse_select_env()
 _select_env = _select

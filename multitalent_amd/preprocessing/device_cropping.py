@@ -7,8 +7,18 @@
   crop_to_nonzero       the two above, ONE device-to-host read of the seven box integers `mt_fill_holes3d` reduces, then
                         `mt_crop_nonzero`: data and segmentation of the box in one pass.
 
+  ImageCropper          the static `crop` / `crop_from_list_of_files` of a single case, and the offline cropper of a dataset
+                        (reference cropping.py:119-216): `run_cropping` writes `<case>.npz` / `<case>.pkl` and `gt_segmentations/`;
+                        `num_threads` host threads read the files and compress the results around the one device stream, and
+                        `properties['classes']` comes from `mt_label_presence`.
+
 There is no CPU labelling here: without a HIP device every function raises (the host path is `cropping.py`).  The data must be
 float32 (what `load_case_from_list_of_files` returns), a given seg float32 too."""
+import os
+import pickle
+import shutil
+from concurrent.futures import ThreadPoolExecutor
+
 import numpy as np
 import torch
 
@@ -92,7 +102,20 @@ def crop_to_nonzero(data, seg=None, nonzero_label=-1):
     return out, seg_out, [[b[0], b[1]], [b[2], b[3]], [b[4], b[5]]]
 
 
+def get_patient_identifiers_from_cropped_files(folder):
+    """cropping.py:119-120: the names of the `.npz` files of a folder without their suffix, sorted."""
+    return sorted(f[:-4] for f in os.listdir(folder) if f.endswith(".npz") and os.path.isfile(os.path.join(folder, f)))
+
+
 class ImageCropper(object):
+    def __init__(self, num_threads, output_folder=None):
+        """num_threads: host threads that read the image files and compress / write the results; output_folder: where the cropped
+        cases go (created when given)."""
+        self.output_folder = output_folder
+        self.num_threads = num_threads
+        if self.output_folder is not None:
+            os.makedirs(self.output_folder, exist_ok=True)
+
     @staticmethod
     def crop(data, properties, seg=None):
         data, seg, bbox = crop_to_nonzero(data, seg, nonzero_label=-1)                # cropping.py:139-150
@@ -109,3 +132,84 @@ class ImageCropper(object):
     def crop_from_list_of_files(data_files, seg_file=None):
         data, seg, properties = load_case_from_list_of_files(data_files, seg_file)
         return ImageCropper.crop(data, properties, seg)
+
+    def _is_done(self, case_identifier):
+        return os.path.isfile(os.path.join(self.output_folder, "%s.npz" % case_identifier)) \
+            and os.path.isfile(os.path.join(self.output_folder, "%s.pkl" % case_identifier))
+
+    @staticmethod
+    def _crop_loaded(data, seg, properties, case_identifier):
+        """`crop` for the offline cropper: the same steps, with `properties['classes']` from `mt_label_presence` instead of a sort of
+        the volume.  -> all_data = vstack((data, seg)) as a host array, properties."""
+        data, seg, bbox = crop_to_nonzero(data, seg, nonzero_label=-1)
+        properties["crop_bbox"] = bbox
+        as_float = seg.dtype == torch.float32
+        with torch.cuda.device(seg.device):
+            labels = ops.label_presence(seg if as_float else seg.float(), "the segmentation of case %s" % case_identifier)
+        properties['classes'] = np.array(labels, dtype=np.float32 if as_float else np.int64)          # np.unique(seg)
+        properties["size_after_cropping"] = tuple(int(i) for i in data[0].shape)
+        return np.vstack((data.cpu().numpy(), seg.cpu().numpy())), properties
+
+    def _save(self, case_identifier, all_data, properties):
+        np.savez_compressed(os.path.join(self.output_folder, "%s.npz" % case_identifier), data=all_data)
+        self.save_properties(case_identifier, properties)
+
+    def load_crop_save(self, case, case_identifier, overwrite_existing=False):
+        """cropping.py:152-170: `case` = the modality files and, last, the segmentation file (or None)."""
+        if not torch.cuda.is_available():
+            _no_device()
+        print(case_identifier)
+        if overwrite_existing or not self._is_done(case_identifier):
+            data, seg, properties = load_case_from_list_of_files(case[:-1], case[-1])
+            self._save(case_identifier, *self._crop_loaded(data, seg, properties, case_identifier))
+
+    def get_list_of_cropped_files(self):
+        return [os.path.join(self.output_folder, i + ".npz") for i in get_patient_identifiers_from_cropped_files(self.output_folder)]
+
+    def get_patient_identifiers_from_cropped_files(self):
+        return [i.split("/")[-1][:-4] for i in self.get_list_of_cropped_files()]
+
+    def run_cropping(self, list_of_files, overwrite_existing=False, output_folder=None):
+        """cropping.py:178-206: list_of_files = [[modality files ..., segmentation file or None], ...].  The ground-truth
+        segmentations are copied to `gt_segmentations/`; a case whose `.npz` and `.pkl` exist is skipped unless
+        `overwrite_existing`.  The cases go through the one device in sequence; host threads read ahead and write behind."""
+        if not torch.cuda.is_available():
+            _no_device()
+        if output_folder is not None:
+            self.output_folder = output_folder
+        output_folder_gt = os.path.join(self.output_folder, "gt_segmentations")
+        os.makedirs(output_folder_gt, exist_ok=True)
+        for case in list_of_files:
+            if case[-1] is not None:
+                shutil.copy(case[-1], output_folder_gt)
+        todo = [(case, get_case_identifier(case)) for case in list_of_files]
+        todo = [(case, ident) for case, ident in todo if overwrite_existing or not self._is_done(ident)]
+        threads = max(1, int(self.num_threads))
+        with ThreadPoolExecutor(max_workers=threads) as pool:
+            reads = [pool.submit(load_case_from_list_of_files, case[:-1], case[-1]) for case, _ in todo[:threads]]
+            writes = []
+            for i, (case, ident) in enumerate(todo):
+                print(ident)
+                try:
+                    data, seg, properties = reads.pop(0).result()
+                    if i + threads < len(todo):                                   # keeps `threads` reads in flight
+                        nxt = todo[i + threads][0]
+                        reads.append(pool.submit(load_case_from_list_of_files, nxt[:-1], nxt[-1]))
+                    all_data, properties = self._crop_loaded(data, seg, properties, ident)
+                except Exception as e:
+                    print("Exception in", ident, ":")
+                    print(e)
+                    raise e
+                writes.append(pool.submit(self._save, ident, all_data, properties))
+                while len(writes) > 2 * threads:                                  # bounds the volumes waiting in host memory
+                    writes.pop(0).result()
+            for w in writes:
+                w.result()
+
+    def load_properties(self, case_identifier):
+        with open(os.path.join(self.output_folder, "%s.pkl" % case_identifier), 'rb') as f:
+            return pickle.load(f)
+
+    def save_properties(self, case_identifier, properties):
+        with open(os.path.join(self.output_folder, "%s.pkl" % case_identifier), 'wb') as f:
+            pickle.dump(properties, f)
