@@ -513,9 +513,13 @@ int mt_label_locations(const float* seg, int D, int H, int W, const uint8_t* tab
  *   floating-point atomics: `out` and `stats` are bit-identical from run to run.
  *   ws: mt_surface_distances_workspace(D, H, W, capacity) bytes of device scratch, 16-byte aligned (5 bytes per voxel and
  *   4 per entry of capacity).  D*H*W > INT32_MAX, or an axis above 32766, is rejected with MT_EINVAL before any launch.
- * mt_select_kth: out[r] (device doubles) = the ranks[r]-th smallest (0-based) of the n non-negative doubles x, for nranks <= 8
- *   HOST ranks: radix select on the bit patterns (non-negative doubles order as uint64).  ws: mt_select_kth_workspace(nranks)
- *   bytes of device scratch, 8-byte aligned. */
+ * mt_select_kth: out[r] (device doubles) = the ranks[r]-th smallest (0-based) of the n doubles x (8-byte aligned; any n >= 1: the
+ *   former limit of 2^32 - 1 elements is gone), for nranks <= 8 HOST ranks: the float64 width of the radix select of mt_select_kth_f32
+ *   below, 8 passes of 8 bits on the key bits ^ (sign ? all ones : sign bit).  The key orders doubles of either sign (-0.0 before
+ *   +0.0, NaNs by bit pattern); among the non-negative doubles the entry point was first specified for it selects exactly the element
+ *   the plain bit pattern selects.  ws: mt_select_kth_workspace(nranks) bytes of device scratch, 8-byte aligned: ask every time, the
+ *   size is not that of earlier builds.  n < 1, a rank outside 0..n-1 or nranks outside 1..8 is MT_EINVAL, too small a workspace
+ *   MT_EWORKSPACE, both before any launch. */
 int mt_seg_joint_hist(const uint8_t* test, const uint8_t* ref, long V, const uint8_t* remap, int C, int64_t* hist, mt_stream_t stream);
 size_t mt_surface_distances_workspace(int D, int H, int W, long capacity);
 int mt_surface_distances(const uint8_t* test, const uint8_t* ref, int D, int H, int W, const uint8_t* member, const double* spacing,

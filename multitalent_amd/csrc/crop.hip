@@ -3,15 +3,9 @@
 //   mt_crop_nonzero   one pass over the crop box: the data channels bit for bit, and the segmentation with `nonzero_label`
 //                     outside the mask.
 // The hole filling between the two is mt_fill_holes3d (postproc.hip: it shares the union-find labelling).
-#include "mt_common.h"
+#include "stream_common.h"
 
 #define CR_THREADS 256
-
-static int cr_stream_blocks(long items) {
-  const int cap = mt_device_cus(mt_current_device()) * 8;
-  const int b = mt_cdiv(items, CR_THREADS);
-  return b < cap ? b : (cap > 0 ? cap : 1);
-}
 
 __device__ __forceinline__ uint32_t cr_nz(uint32_t bits) { return (bits & 0x7fffffffu) != 0 ? 1u : 0u; }
 
@@ -57,7 +51,7 @@ extern "C" int mt_nonzero_mask(const float* data, int C, long V, uint8_t* mask, 
   if (head > V) head = V;
   const long nquad = (V - head) / 4;
   const long items = nquad ? (nquad + 1) / 2 : V;
-  hipLaunchKernelGGL(nz_mask_kernel, dim3(cr_stream_blocks(items)), dim3(CR_THREADS), 0, (hipStream_t)stream, (const uint32_t*)data, C, V,
+  hipLaunchKernelGGL(nz_mask_kernel, dim3(mt_stream_blocks(items, CR_THREADS)), dim3(CR_THREADS), 0, (hipStream_t)stream, (const uint32_t*)data, C, V,
                      head, nquad, mask);
   MT_CHECK_LAUNCH("nonzero_mask");
   return MT_OK;
@@ -105,12 +99,12 @@ extern "C" int mt_crop_nonzero(const float* data, int C, int D, int H, int W, co
   const uint32_t bits = __builtin_bit_cast(uint32_t, nonzero_label);
   hipStream_t s = (hipStream_t)stream;
   if (seg_in) {
-    hipLaunchKernelGGL(crop_kernel<1>, dim3(cr_stream_blocks(Vo)), dim3(CR_THREADS), 0, s, (const uint32_t*)data, C, V, mask, g,
+    hipLaunchKernelGGL(crop_kernel<1>, dim3(mt_stream_blocks(Vo, CR_THREADS)), dim3(CR_THREADS), 0, s, (const uint32_t*)data, C, V, mask, g,
                        (uint32_t*)out, (const uint32_t*)seg_in, CS, seg_out, bits, 0);
   } else {
     MT_REQUIRE(nonzero_label >= -128.f && nonzero_label <= 127.f && nonzero_label == (float)(int)nonzero_label,
                "crop_nonzero: nonzero_label %g is not an int8 value", (double)nonzero_label);
-    hipLaunchKernelGGL(crop_kernel<0>, dim3(cr_stream_blocks(Vo)), dim3(CR_THREADS), 0, s, (const uint32_t*)data, C, V, mask, g,
+    hipLaunchKernelGGL(crop_kernel<0>, dim3(mt_stream_blocks(Vo, CR_THREADS)), dim3(CR_THREADS), 0, s, (const uint32_t*)data, C, V, mask, g,
                        (uint32_t*)out, (const uint32_t*)nullptr, 0, seg_out, bits, (int)nonzero_label);
   }
   MT_CHECK_LAUNCH("crop_nonzero");

@@ -13,16 +13,10 @@
 //                          each row's candidate from g1, until no unvisited row can be nearer; the distance is
 //                          sqrt((dz sz)^2 + (dy sy)^2 + (dx sx)^2) in fp64 of the integer offsets to the site found;
 //     sd_reduce_kernel x2  count, maximum and sum per direction: fixed 4096-element chunks, fixed tree, no atomics.
-//   mt_select_kth          k-th smallest of non-negative doubles: radix select, 8 bits a pass, on the uint64 bit patterns.
 // Every floating-point result is a function of the inputs alone (integer atomics only): two runs are bit-identical.
-#include "mt_common.h"
+#include "stream_common.h"
 
 #define MX_THREADS 256
-
-struct MxMember { uint32_t bits[8]; };   // 256-bit membership of the uint8 labels
-__device__ __forceinline__ bool mx_member(const MxMember& m, uint8_t v) { return (m.bits[v >> 5] >> (v & 31)) & 1u; }
-
-static int mx_stream_cap() { return mt_device_cus(mt_current_device()) * 8; }
 
 // ---- joint label histogram -------------------------------------------------------------------------------------------------
 struct SegRemap { uint32_t w[64]; };     // remap[v] = byte v
@@ -100,7 +94,7 @@ extern "C" int mt_seg_joint_hist(const uint8_t* test, const uint8_t* ref, long V
   else head = 0;                                      // different misalignment: everything bytewise
   const long items = nvec ? nvec : V;
   long grid = (items + MX_THREADS - 1) / MX_THREADS;
-  const long cap = mx_stream_cap(), need = (V >> 30) + 1;     // a workgroup's int32 LDS counts stay below 2^31
+  const long cap = mt_stream_cap(), need = (V >> 30) + 1;     // a workgroup's int32 LDS counts stay below 2^31
   if (grid > cap) grid = cap > need ? cap : need;
   if (C <= SH_LDS_MAXC)
     hipLaunchKernelGGL(seg_hist_kernel<true>, dim3((unsigned)grid), dim3(MX_THREADS), 0, s, test, ref, V, head, nvec, rm, C,
@@ -125,7 +119,7 @@ struct SDGeom { int D, H, W; double sz, sy, sx; };
 // border(X) = X ^ binary_erosion(X, generate_binary_structure(3, conn)), border_value 0: a mask voxel is a border voxel when a
 // neighbour of the structure (city-block distance <= conn inside the 3x3x3 cube) is outside the mask or outside the volume.
 __global__ __launch_bounds__(MX_THREADS) void sd_border_kernel(const uint8_t* __restrict__ test, const uint8_t* __restrict__ ref,
-                                                               const MxMember m, const SDGeom g, int conn, long V,
+                                                               const MtMember m, const SDGeom g, int conn, long V,
                                                                uint8_t* __restrict__ bm, int32_t* __restrict__ cnt) {
   __shared__ int red[4][2];
   int na = 0, nb = 0;                                         // wave-uniform
@@ -134,7 +128,7 @@ __global__ __launch_bounds__(MX_THREADS) void sd_border_kernel(const uint8_t* __
     const long v = base + j * MX_THREADS + threadIdx.x;
     bool ba = false, bb = false;
     if (v < V) {
-      const bool a = mx_member(m, test[v]), b = mx_member(m, ref[v]);
+      const bool a = mt_member(m, test[v]), b = mt_member(m, ref[v]);
       if (a | b) {
         const int w = (int)(v % g.W), h = (int)((v / g.W) % g.H), d = (int)(v / ((long)g.W * g.H));
         bool ea = a, eb = b;
@@ -146,8 +140,8 @@ __global__ __launch_bounds__(MX_THREADS) void sd_border_kernel(const uint8_t* __
               const int zz = d + dz, yy = h + dy, xx = w + dx;
               if (zz < 0 || zz >= g.D || yy < 0 || yy >= g.H || xx < 0 || xx >= g.W) { ea = false; eb = false; continue; }
               const long nv = ((long)zz * g.H + yy) * g.W + xx;
-              if (ea) ea = mx_member(m, test[nv]);
-              if (eb) eb = mx_member(m, ref[nv]);
+              if (ea) ea = mt_member(m, test[nv]);
+              if (eb) eb = mt_member(m, ref[nv]);
             }
         ba = a && !ea;
         bb = b && !eb;
@@ -434,9 +428,7 @@ extern "C" int mt_surface_distances(const uint8_t* test, const uint8_t* ref, int
   const SDLayout L = sd_layout(V, D, H, capacity);
   MT_REQUIRE(ws_bytes >= L.total, "surface_distances: workspace of %zu bytes, %zu needed", ws_bytes, L.total);
   MT_REQUIRE(((uintptr_t)ws & 15) == 0, "surface_distances: workspace must be 16-byte aligned");
-  MxMember m;
-  for (int k = 0; k < 8; ++k) m.bits[k] = 0;
-  for (int k = 0; k < 256; ++k) if (member[k]) m.bits[k >> 5] |= 1u << (k & 31);
+  const MtMember m = mt_member_from_bytes(member);
   char* base = (char*)ws;
   uint8_t* bm = (uint8_t*)(base + L.bm);
   short* g1 = (short*)(base + L.g1);
@@ -460,13 +452,13 @@ extern "C" int mt_surface_distances(const uint8_t* test, const uint8_t* ref, int
   hipLaunchKernelGGL(sd_compact_kernel, dim3(nblk), dim3(MX_THREADS), 0, s, bm, V, off, tot, capacity, q);
   MT_CHECK_LAUNCH("surface_distances (compact)");
   const long nrows = (long)D * H;
-  const int cap_blocks = mx_stream_cap();
+  const long cap_blocks = mt_stream_cap();
   long rgrid = (nrows + 3) / 4;
-  if (rgrid > cap_blocks * 4L) rgrid = cap_blocks * 4L;
+  if (rgrid > cap_blocks * 4) rgrid = cap_blocks * 4;
   hipLaunchKernelGGL(sd_rows_kernel, dim3((unsigned)rgrid), dim3(MX_THREADS), 0, s, bm, g, nrows, (short2*)g1, pflag, rflag);
   MT_CHECK_LAUNCH("surface_distances (rows)");
   long qgrid = (capacity + MX_THREADS - 1) / MX_THREADS;
-  if (qgrid > cap_blocks * 4L) qgrid = cap_blocks * 4L;
+  if (qgrid > cap_blocks * 4) qgrid = cap_blocks * 4;
   hipLaunchKernelGGL(sd_query_kernel, dim3((unsigned)qgrid), dim3(MX_THREADS), 0, s, q, tot, capacity, g1, pflag, rflag, g, out);
   MT_CHECK_LAUNCH("surface_distances (query)");
   long pgrid = L.maxchunks < cap_blocks ? L.maxchunks : cap_blocks;
@@ -474,95 +466,5 @@ extern "C" int mt_surface_distances(const uint8_t* test, const uint8_t* ref, int
   MT_CHECK_LAUNCH("surface_distances (reduce 1)");
   hipLaunchKernelGGL(sd_reduce2_kernel, dim3(1), dim3(MX_THREADS), 0, s, partial, tot, capacity, L.maxchunks, stats);
   MT_CHECK_LAUNCH("surface_distances (reduce 2)");
-  return MT_OK;
-}
-
-// ---- k-th smallest (radix select) ------------------------------------------------------------------------------------------
-#define SEL_MAXRANKS 8
-struct SelRanks { unsigned long long k[SEL_MAXRANKS]; };
-struct SelState {                          // the workspace
-  unsigned long long prefix[SEL_MAXRANKS]; // the digits found so far (high bits of the answer)
-  unsigned long long k[SEL_MAXRANKS];      // rank among the elements that share the prefix
-  unsigned long long hist[SEL_MAXRANKS][256];
-};
-
-__global__ __launch_bounds__(MX_THREADS) void sel_hist_kernel(const unsigned long long* __restrict__ x, long n, int pass, int nr,
-                                                              SelState* __restrict__ st) {
-  __shared__ unsigned lh[SEL_MAXRANKS][256];
-  __shared__ unsigned long long pre[SEL_MAXRANKS];
-  for (int i = threadIdx.x; i < nr * 256; i += MX_THREADS) lh[i >> 8][i & 255] = 0;
-  if ((int)threadIdx.x < nr) pre[threadIdx.x] = st->prefix[threadIdx.x];
-  __syncthreads();
-  const int shift = 56 - 8 * pass;
-  // a workgroup adds at most 2^32 - 1 elements to its LDS bins: n <= 2^32 - 1 is required by the entry point
-  for (long i = (long)blockIdx.x * MX_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * MX_THREADS) {
-    const unsigned long long key = x[i];
-    const unsigned long long hi = pass ? key >> (shift + 8) : 0ull;
-    const unsigned digit = (unsigned)(key >> shift) & 255u;
-    for (int r = 0; r < nr; ++r)
-      if (hi == pre[r]) atomicAdd(&lh[r][digit], 1u);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nr * 256; i += MX_THREADS)
-    if (lh[i >> 8][i & 255]) atomicAdd(&st->hist[i >> 8][i & 255], (unsigned long long)lh[i >> 8][i & 255]);
-}
-
-// Thread r walks rank r's 256 bins to the one that holds its k, then the bins are cleared for the next pass.
-__global__ __launch_bounds__(MX_THREADS) void sel_pick_kernel(SelState* __restrict__ st, int nr, int last, double* __restrict__ out) {
-  const int r = threadIdx.x;
-  if (r < nr) {
-    unsigned long long k = st->k[r], cum = 0;
-    int digit = 255;
-    for (int b = 0; b < 256; ++b) {
-      const unsigned long long h = st->hist[r][b];
-      if (cum + h > k) { digit = b; break; }
-      cum += h;
-    }
-    const unsigned long long p = (st->prefix[r] << 8) | (unsigned long long)digit;
-    st->prefix[r] = p;
-    st->k[r] = k - cum;
-    if (last) out[r] = __builtin_bit_cast(double, p);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nr * 256; i += MX_THREADS) st->hist[i >> 8][i & 255] = 0;
-}
-
-__global__ void sel_init_kernel(SelState* __restrict__ st, const SelRanks ranks) {
-#pragma unroll
-  for (int r = 0; r < SEL_MAXRANKS; ++r)
-    if ((int)threadIdx.x == r) { st->prefix[r] = 0; st->k[r] = ranks.k[r]; }
-  for (int i = threadIdx.x; i < SEL_MAXRANKS * 256; i += blockDim.x) st->hist[i >> 8][i & 255] = 0;
-}
-
-extern "C" size_t mt_select_kth_workspace(int nranks) {
-  return nranks >= 1 && nranks <= SEL_MAXRANKS ? sizeof(SelState) : 0;
-}
-
-extern "C" int mt_select_kth(const double* x, long n, const long* ranks, int nranks, double* out, void* ws, size_t ws_bytes,
-                             mt_stream_t stream) {
-  MT_REQUIRE(x && ranks && out && ws, "select_kth: null pointer");
-  MT_REQUIRE(n >= 1 && n <= 0xffffffffL, "select_kth: bad element count %ld", n);
-  MT_REQUIRE(nranks >= 1 && nranks <= SEL_MAXRANKS, "select_kth: %d ranks (1..%d)", nranks, SEL_MAXRANKS);
-  MT_REQUIRE(ws_bytes >= sizeof(SelState) && ((uintptr_t)ws & 7) == 0, "select_kth: workspace of %zu bytes, %zu needed (8-byte aligned)",
-             ws_bytes, sizeof(SelState));
-  SelRanks rk;
-  for (int r = 0; r < SEL_MAXRANKS; ++r) rk.k[r] = 0;
-  for (int r = 0; r < nranks; ++r) {
-    MT_REQUIRE(ranks[r] >= 0 && ranks[r] < n, "select_kth: rank %ld outside 0..%ld", ranks[r], n - 1);
-    rk.k[r] = (unsigned long long)ranks[r];
-  }
-  SelState* st = (SelState*)ws;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(sel_init_kernel, dim3(1), dim3(MX_THREADS), 0, s, st, rk);
-  MT_CHECK_LAUNCH("select_kth (init)");
-  long grid = (n + MX_THREADS - 1) / MX_THREADS;
-  const long cap = mx_stream_cap();
-  if (grid > cap) grid = cap;
-  for (int pass = 0; pass < 8; ++pass) {
-    hipLaunchKernelGGL(sel_hist_kernel, dim3((unsigned)grid), dim3(MX_THREADS), 0, s, (const unsigned long long*)x, n, pass, nranks, st);
-    MT_CHECK_LAUNCH("select_kth (histogram)");
-    hipLaunchKernelGGL(sel_pick_kernel, dim3(1), dim3(MX_THREADS), 0, s, st, nranks, pass == 7 ? 1 : 0, out);
-    MT_CHECK_LAUNCH("select_kth (pick)");
-  }
   return MT_OK;
 }

@@ -20,6 +20,15 @@ void mt_set_error(const char* fmt, ...);
     }                                    \
   } while (0)
 
+#define MT_REQUIRE_WORKSPACE(who, have, need)                                              \
+  do {                                                                                   \
+    const size_t have_ = (have), need_ = (need);                                         \
+    if (have_ < need_) {                                                                 \
+      mt_set_error("%s: workspace of %zu bytes, %zu needed", who, have_, need_);         \
+      return MT_EWORKSPACE;                                                              \
+    }                                                                                    \
+  } while (0)
+
 #define MT_CHECK_LAUNCH(name)                                                  \
   do {                                                                         \
     hipError_t e_ = hipGetLastError();                                         \

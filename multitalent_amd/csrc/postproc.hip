@@ -17,17 +17,13 @@
 //   fh_mark_kernel       every background voxel on one of the six faces of the volume stores -2 over its root's own label;
 //   fh_fill_kernel       mask[v] = 1 where v is foreground or its component's root is unmarked (a cavity), else 0, and the
 //                        bounding box and count of the result: wave shuffles, then one integer atomic per workgroup and value.
-#include "mt_common.h"
+#include "stream_common.h"
 
 #define CC_BD 8
 #define CC_BH 16
 #define CC_BW 16
 #define CC_BV (CC_BD * CC_BH * CC_BW)   // 2048 voxels per brick, 8 per thread
 #define CC_THREADS 256
-
-struct CCMember { uint32_t bits[8]; };   // 256-bit membership of the uint8 labels
-
-__device__ __forceinline__ bool cc_member(const CCMember& m, uint8_t v) { return (m.bits[v >> 5] >> (v & 31)) & 1u; }
 
 // ---- LDS union-find (one workgroup) ----------------------------------------------------------------------------------------
 __device__ __forceinline__ int cc_lds_load(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -80,7 +76,7 @@ __device__ __forceinline__ void cc_brick_origin(const CCGeom& g, int b, int& d0,
 
 // COUNT = false (mt_fill_holes3d): no piece counts, S is not touched and may be NULL.
 template <bool COUNT>
-__global__ __launch_bounds__(CC_THREADS) void cc_local_kernel(const uint8_t* __restrict__ seg, const CCMember m, const CCGeom g,
+__global__ __launch_bounds__(CC_THREADS) void cc_local_kernel(const uint8_t* __restrict__ seg, const MtMember m, const CCGeom g,
                                                               int nb, int32_t* __restrict__ L, int32_t* __restrict__ S,
                                                               int32_t* __restrict__ stats) {
   __shared__ int par[CC_BV];
@@ -101,7 +97,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_local_kernel(const uint8_t* __r
     for (int ld = 0; ld < CC_BD; ++ld) {
       const int d = d0 + ld, i = ld * (CC_BH * CC_BW) + t;
       bool f = false;
-      if (hw_in && d < g.D) f = cc_member(m, seg[((size_t)d * g.H + h) * g.W + w]);
+      if (hw_in && d < g.D) f = mt_member(m, seg[((size_t)d * g.H + h) * g.W + w]);
       const unsigned row = (unsigned)(__ballot(f) >> (t & 48)) & 0xffffu;
       const unsigned below = ~row & ((1u << lw) - 1u);               // voxels before lw that are not in the mask
       const int start = below ? 32 - __clz((int)below) : 0;
@@ -283,16 +279,10 @@ __global__ __launch_bounds__(CC_THREADS) void cc_remove_kernel(uint8_t* __restri
   if (threadIdx.x == 0 && m) atomicMax(removed, m);
 }
 
-static int cc_stream_blocks(long V) {
-  const int cap = mt_device_cus(mt_current_device()) * 8;
-  const int b = mt_cdiv(V, CC_THREADS);
-  return b < cap ? b : cap;
-}
-
 // The labelling launches shared by mt_cc_label3d and mt_fill_holes3d: local, merge, flatten (labels[v] = root, stats[0] = number
 // of components, stats[1] = 0).  COUNT: the local kernel also writes the brick-local piece counts into sizes.
 template <bool COUNT>
-static int cc_label_launches(const uint8_t* seg, int D, int H, int W, const CCMember& m, int32_t* labels, int32_t* sizes,
+static int cc_label_launches(const uint8_t* seg, int D, int H, int W, const MtMember& m, int32_t* labels, int32_t* sizes,
                              int32_t* stats, hipStream_t s, const char* who) {
   const long V = (long)D * H * W;
   CCGeom g;
@@ -303,7 +293,7 @@ static int cc_label_launches(const uint8_t* seg, int D, int H, int W, const CCMe
   MT_CHECK_LAUNCH(who);
   hipLaunchKernelGGL(cc_merge_kernel, dim3(grid), dim3(CC_THREADS), 0, s, g, (int)nb, labels);
   MT_CHECK_LAUNCH(who);
-  hipLaunchKernelGGL(cc_flatten_kernel, dim3(cc_stream_blocks(V)), dim3(CC_THREADS), 0, s, labels, V, stats);
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(mt_stream_blocks(V, CC_THREADS)), dim3(CC_THREADS), 0, s, labels, V, stats);
   MT_CHECK_LAUNCH(who);
   return MT_OK;
 }
@@ -314,13 +304,11 @@ extern "C" int mt_cc_label3d(const uint8_t* seg, int D, int H, int W, const uint
   MT_REQUIRE(D > 0 && H > 0 && W > 0, "cc_label3d: bad shape %d x %d x %d", D, H, W);
   const long V = (long)D * H * W;
   MT_REQUIRE(V <= (long)INT32_MAX, "cc_label3d: %ld voxels exceed the int32 index range", V);
-  CCMember m;
-  for (int k = 0; k < 8; ++k) m.bits[k] = 0;
-  for (int k = 0; k < 256; ++k) if (member[k]) m.bits[k >> 5] |= 1u << (k & 31);
+  const MtMember m = mt_member_from_bytes(member);
   hipStream_t s = (hipStream_t)stream;
   const int rc = cc_label_launches<true>(seg, D, H, W, m, labels, sizes, stats, s, "cc_label3d (labelling)");
   if (rc != MT_OK) return rc;
-  hipLaunchKernelGGL(cc_count_kernel, dim3(cc_stream_blocks(V)), dim3(CC_THREADS), 0, s, labels, sizes, V, stats);
+  hipLaunchKernelGGL(cc_count_kernel, dim3(mt_stream_blocks(V, CC_THREADS)), dim3(CC_THREADS), 0, s, labels, sizes, V, stats);
   MT_CHECK_LAUNCH("cc_label3d (count)");
   return MT_OK;
 }
@@ -336,7 +324,7 @@ extern "C" int mt_cc_remove(uint8_t* seg, int D, int H, int W, const int32_t* la
     mt_set_error("cc_remove: hipMemsetAsync failed");
     return MT_EHIP;
   }
-  hipLaunchKernelGGL(cc_remove_kernel, dim3(cc_stream_blocks(V)), dim3(CC_THREADS), 0, s, seg, labels, sizes, V, stats,
+  hipLaunchKernelGGL(cc_remove_kernel, dim3(mt_stream_blocks(V, CC_THREADS)), dim3(CC_THREADS), 0, s, seg, labels, sizes, V, stats,
                      volume_per_voxel, min_size, use_min_size, removed);
   MT_CHECK_LAUNCH("cc_remove");
   return MT_OK;
@@ -452,22 +440,18 @@ extern "C" int mt_fill_holes3d(uint8_t* mask, int D, int H, int W, int32_t* bbox
   const long V = (long)D * H * W;
   MT_REQUIRE(V <= (long)INT32_MAX, "fill_holes3d: %ld voxels exceed the int32 index range", V);
   MT_REQUIRE(((uintptr_t)ws & 15) == 0, "fill_holes3d: the workspace must be 16-byte aligned");
-  if (ws_bytes < mt_fill_holes3d_workspace(D, H, W)) {
-    mt_set_error("fill_holes3d: workspace of %zu bytes, %zu needed", ws_bytes, mt_fill_holes3d_workspace(D, H, W));
-    return MT_EWORKSPACE;
-  }
+  MT_REQUIRE_WORKSPACE("fill_holes3d", ws_bytes, mt_fill_holes3d_workspace(D, H, W));
   int32_t* labels = (int32_t*)ws;
   int32_t* stats = (int32_t*)((char*)ws + fh_label_bytes(V));
-  CCMember m;
-  for (int k = 0; k < 8; ++k) m.bits[k] = 0;
-  m.bits[0] = 1u;                                                    // the background: mask == 0
+  const uint8_t background[256] = {1};                               // mask == 0 only
+  const MtMember m = mt_member_from_bytes(background);
   hipStream_t s = (hipStream_t)stream;
   const int rc = cc_label_launches<false>(mask, D, H, W, m, labels, nullptr, stats, s, "fill_holes3d (labelling)");
   if (rc != MT_OK) return rc;
   const long faces = 2 * ((long)H * W + (long)D * W + (long)D * H);
-  hipLaunchKernelGGL(fh_mark_kernel, dim3(cc_stream_blocks(faces)), dim3(CC_THREADS), 0, s, labels, D, H, W, bbox);
+  hipLaunchKernelGGL(fh_mark_kernel, dim3(mt_stream_blocks(faces, CC_THREADS)), dim3(CC_THREADS), 0, s, labels, D, H, W, bbox);
   MT_CHECK_LAUNCH("fill_holes3d (mark)");
-  hipLaunchKernelGGL(fh_fill_kernel, dim3(cc_stream_blocks((V + 15) / 16)), dim3(CC_THREADS), 0, s, mask, labels, H, W, V,
+  hipLaunchKernelGGL(fh_fill_kernel, dim3(mt_stream_blocks((V + 15) / 16, CC_THREADS)), dim3(CC_THREADS), 0, s, mask, labels, H, W, V,
                      (int)(((uintptr_t)mask & 15) == 0), bbox);
   MT_CHECK_LAUNCH("fill_holes3d (fill)");
   return MT_OK;

@@ -7,21 +7,12 @@
 //   mt_label_locations       np.argwhere(seg == c)[rank] for a list of (class, rank) queries, through that compaction.
 // All of them stream the volume once per pass (HBM-bound).  Every sum is formed in a fixed order and the compaction uses integer
 // counts only: results are bit-identical from run to run, whatever the block scheduling.
-#include "mt_common.h"
+#include "stream_common.h"
 #include <math.h>
 
 #define PP_THREADS 256
 #define PP_WAVES (PP_THREADS / MT_WAVE)
 #define PP_MAX_CHANNELS 16
-
-static int pp_stream_blocks(long items) {
-  const int cap = mt_device_cus(mt_current_device()) * 8;
-  const int b = mt_cdiv(items, PP_THREADS);
-  return b < cap ? (b > 0 ? b : 1) : (cap > 0 ? cap : 1);
-}
-
-// 16 bytes that are only dword aligned (channel c starts at data + c * V): gfx950 serves a dword-aligned global_load_dwordx4.
-struct __attribute__((packed, aligned(4))) pp_f4 { float x, y, z, w; };
 
 // ---- masked moments ----------------------------------------------------------------------------------------------------------
 struct MomParams {
@@ -49,9 +40,9 @@ __global__ __launch_bounds__(PP_THREADS) void moments_kernel(const MomParams P) 
   const long gtid = (long)blockIdx.x * PP_THREADS + threadIdx.x, gstride = (long)gridDim.x * PP_THREADS;
   double sum = 0.0, cnt = 0.0;
   for (long q = gtid; q < nquad; q += gstride) {
-    const pp_f4 a = *(const pp_f4*)(x + 4 * q);
-    pp_f4 s = {0.f, 0.f, 0.f, 0.f};
-    if (PRED == MT_MOMENTS_SEG_GE0) s = *(const pp_f4*)(P.seg + 4 * q);
+    const mt_f4 a = *(const mt_f4*)(x + 4 * q);
+    mt_f4 s = {0.f, 0.f, 0.f, 0.f};
+    if (PRED == MT_MOMENTS_SEG_GE0) s = *(const mt_f4*)(P.seg + 4 * q);
     const float av[4] = {a.x, a.y, a.z, a.w}, sv[4] = {s.x, s.y, s.z, s.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k)
@@ -98,7 +89,7 @@ __global__ __launch_bounds__(MT_WAVE) void moments_finalize_kernel(const double*
   }
 }
 
-static int pp_moment_blocks(long V) { return pp_stream_blocks((V + 3) / 4); }
+static int pp_moment_blocks(long V) { return mt_stream_blocks((V + 3) / 4, PP_THREADS); }
 
 extern "C" size_t mt_masked_moments_workspace(int C, long V) {
   if (C < 1 || V < 1) return 0;
@@ -114,10 +105,7 @@ extern "C" int mt_masked_moments(const float* data, int C, long V, int pred, con
   MT_REQUIRE(pred != MT_MOMENTS_OPEN_RANGE || (lo && hi), "masked_moments: the range predicate needs lo and hi");
   MT_REQUIRE(((uintptr_t)data & 3) == 0 && ((uintptr_t)seg & 3) == 0 && ((uintptr_t)stats & 7) == 0 && ((uintptr_t)ws & 7) == 0,
              "masked_moments: misaligned pointer");
-  if (ws_bytes < mt_masked_moments_workspace(C, V)) {
-    mt_set_error("masked_moments: workspace of %zu bytes, %zu needed", ws_bytes, mt_masked_moments_workspace(C, V));
-    return MT_EWORKSPACE;
-  }
+  MT_REQUIRE_WORKSPACE("masked_moments", ws_bytes, mt_masked_moments_workspace(C, V));
   MomParams P;
   P.data = data; P.seg = seg; P.V = V; P.pred = pred; P.nblk = pp_moment_blocks(V); P.part = (double*)ws; P.stats = stats;
   for (int c = 0; c < PP_MAX_CHANNELS; ++c) {
@@ -156,12 +144,12 @@ __global__ __launch_bounds__(PP_THREADS) void normalize_kernel(const NormParams 
   const long nquad = P.V / 4;
   const long gtid = (long)blockIdx.x * PP_THREADS + threadIdx.x, gstride = (long)gridDim.x * PP_THREADS;
   for (long q = gtid; q < nquad; q += gstride) {
-    pp_f4 a = *(const pp_f4*)(P.x + 4 * q);
-    pp_f4 s = {0.f, 0.f, 0.f, 0.f};
-    if (P.masked) s = *(const pp_f4*)(P.seg + 4 * q);
+    mt_f4 a = *(const mt_f4*)(P.x + 4 * q);
+    mt_f4 s = {0.f, 0.f, 0.f, 0.f};
+    if (P.masked) s = *(const mt_f4*)(P.seg + 4 * q);
     a.x = pp_norm1(a.x, s.x, P, mean, den); a.y = pp_norm1(a.y, s.y, P, mean, den);
     a.z = pp_norm1(a.z, s.z, P, mean, den); a.w = pp_norm1(a.w, s.w, P, mean, den);
-    *(pp_f4*)(P.x + 4 * q) = a;
+    *(mt_f4*)(P.x + 4 * q) = a;
   }
   for (long v = 4 * nquad + gtid; v < P.V; v += gstride) P.x[v] = pp_norm1(P.x[v], P.masked ? P.seg[v] : 0.f, P, mean, den);
 }
@@ -174,7 +162,7 @@ extern "C" int mt_intensity_normalize(float* x, long V, int clip, float lo, floa
   NormParams P;
   P.x = x; P.seg = seg; P.V = V; P.clip = clip ? 1 : 0; P.masked = seg ? 1 : 0; P.lo = lo; P.hi = hi; P.mean = mean; P.sd = sd; P.eps = eps;
   P.stats = stats;
-  hipLaunchKernelGGL(normalize_kernel, dim3(pp_stream_blocks((V + 3) / 4)), dim3(PP_THREADS), 0, (hipStream_t)stream, P);
+  hipLaunchKernelGGL(normalize_kernel, dim3(pp_moment_blocks(V)), dim3(PP_THREADS), 0, (hipStream_t)stream, P);
   MT_CHECK_LAUNCH("intensity_normalize");
   return MT_OK;
 }
@@ -210,7 +198,7 @@ __global__ __launch_bounds__(PP_THREADS) void label_units_kernel(const LabelPara
     int32_t c[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) c[k] = WRITE ? -1 : 0;
-    const long v0 = unit * MT_PP_UNIT, vend = (v0 + MT_PP_UNIT < P.V) ? v0 + MT_PP_UNIT : P.V;
+    const long v0 = unit * MT_PP_UNIT, vend = mt_unit_end(v0, P.V);
     for (long vb = v0; vb < vend; vb += 4 * MT_WAVE) {
       float f[4];
 #pragma unroll
@@ -253,23 +241,9 @@ __global__ __launch_bounds__(PP_THREADS) void label_units_kernel(const LabelPara
 }
 
 // One block per slot: counts of the units -> exclusive offsets in place, total -> counts[slot].
-__global__ __launch_bounds__(PP_THREADS) void label_scan_kernel(int32_t* __restrict__ off, long nunits, int64_t* __restrict__ counts) {
-  int32_t* p = off + (size_t)blockIdx.x * nunits;
-  const long per = (nunits + PP_THREADS - 1) / PP_THREADS;
-  const long b = threadIdx.x * per, e = b + per < nunits ? b + per : nunits;
-  long sum = 0;
-  for (long u = b; u < e; ++u) sum += p[u];
-  __shared__ long sh[PP_THREADS];
-  sh[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    long run = 0;
-    for (int t = 0; t < PP_THREADS; ++t) { const long n = sh[t]; sh[t] = run; run += n; }
-    counts[blockIdx.x] = run;
-  }
-  __syncthreads();
-  long run = sh[threadIdx.x];
-  for (long u = b; u < e; ++u) { const int32_t n = p[u]; p[u] = (int32_t)run; run += n; }
+__global__ __launch_bounds__(MT_SCAN_THREADS) void label_scan_kernel(int32_t* __restrict__ off, long nunits, int64_t* __restrict__ counts) {
+  const int64_t total = mt_scan_units(off + (size_t)blockIdx.x * nunits, nunits);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 __global__ void label_base_kernel(const int64_t* __restrict__ counts, int nslots, int64_t* __restrict__ base) {
@@ -298,11 +272,9 @@ __global__ __launch_bounds__(PP_THREADS) void label_gather_kernel(const int32_t*
   }
 }
 
-static long pp_units(long V) { return (V + MT_PP_UNIT - 1) / MT_PP_UNIT; }
-
 extern "C" size_t mt_label_counts_workspace(long V, int nslots) {
   if (V < 1 || nslots < 1) return 0;
-  return PP_BASE_ENTRIES * sizeof(int64_t) + (size_t)nslots * pp_units(V) * sizeof(int32_t);
+  return PP_BASE_ENTRIES * sizeof(int64_t) + (size_t)nslots * mt_units(V) * sizeof(int32_t);
 }
 
 static int pp_label_args(const char* who, const float* seg, long V, const uint8_t* table, int L, int nslots, void* ws, size_t ws_bytes) {
@@ -310,17 +282,8 @@ static int pp_label_args(const char* who, const float* seg, long V, const uint8_
   MT_REQUIRE(V > 0 && L >= 1 && nslots >= 1 && nslots <= 255, "%s: bad arguments (V %ld, table of %d, %d classes; at most 255)", who, V, L, nslots);
   MT_REQUIRE(V <= (long)INT32_MAX, "%s: %ld voxels exceed the int32 index range", who, V);
   MT_REQUIRE(((uintptr_t)seg & 3) == 0 && ((uintptr_t)ws & 7) == 0, "%s: misaligned pointer", who);
-  if (ws_bytes < mt_label_counts_workspace(V, nslots)) {
-    mt_set_error("%s: workspace of %zu bytes, %zu needed", who, ws_bytes, mt_label_counts_workspace(V, nslots));
-    return MT_EWORKSPACE;
-  }
+  MT_REQUIRE_WORKSPACE(who, ws_bytes, mt_label_counts_workspace(V, nslots));
   return MT_OK;
-}
-
-static int pp_unit_blocks(long nunits) {
-  const int cap = mt_device_cus(mt_current_device()) * 8;
-  const int b = mt_cdiv(nunits, PP_WAVES);
-  return b < cap ? b : (cap > 0 ? cap : 1);
 }
 
 extern "C" int mt_label_counts(const float* seg, long V, const uint8_t* table, int L, int nslots, int64_t* counts, void* ws, size_t ws_bytes,
@@ -329,11 +292,11 @@ extern "C" int mt_label_counts(const float* seg, long V, const uint8_t* table, i
   if (rc != MT_OK) return rc;
   MT_REQUIRE(counts && ((uintptr_t)counts & 7) == 0, "label_counts: counts must be an 8-byte aligned device pointer");
   LabelParams P;
-  P.seg = seg; P.V = V; P.table = table; P.L = L; P.nslots = nslots; P.nunits = pp_units(V);
+  P.seg = seg; P.V = V; P.table = table; P.L = L; P.nslots = nslots; P.nunits = mt_units(V);
   P.base = (int64_t*)ws; P.off = (int32_t*)((int64_t*)ws + PP_BASE_ENTRIES); P.idx = nullptr; P.cap = 0;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(label_units_kernel<false>, dim3(pp_unit_blocks(P.nunits)), dim3(PP_THREADS), 0, s, P);
-  hipLaunchKernelGGL(label_scan_kernel, dim3(nslots), dim3(PP_THREADS), 0, s, P.off, P.nunits, counts);
+  hipLaunchKernelGGL(label_units_kernel<false>, dim3(mt_stream_blocks(P.nunits, PP_WAVES)), dim3(PP_THREADS), 0, s, P);
+  hipLaunchKernelGGL(label_scan_kernel, dim3(nslots), dim3(MT_SCAN_THREADS), 0, s, P.off, P.nunits, counts);
   hipLaunchKernelGGL(label_base_kernel, dim3(1), dim3(1), 0, s, (const int64_t*)counts, nslots, P.base);
   MT_CHECK_LAUNCH("label_counts");
   return MT_OK;
@@ -350,11 +313,11 @@ extern "C" int mt_label_locations(const float* seg, int D, int H, int W, const u
   MT_REQUIRE(((uintptr_t)idx & 3) == 0 && ((uintptr_t)qslot & 3) == 0 && ((uintptr_t)qrank & 7) == 0 && ((uintptr_t)out & 7) == 0,
              "label_locations: misaligned pointer");
   LabelParams P;
-  P.seg = seg; P.V = V; P.table = table; P.L = L; P.nslots = nslots; P.nunits = pp_units(V);
+  P.seg = seg; P.V = V; P.table = table; P.L = L; P.nslots = nslots; P.nunits = mt_units(V);
   P.base = (int64_t*)ws; P.off = (int32_t*)((int64_t*)ws + PP_BASE_ENTRIES); P.idx = idx; P.cap = idx_capacity;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(label_units_kernel<true>, dim3(pp_unit_blocks(P.nunits)), dim3(PP_THREADS), 0, s, P);
-  hipLaunchKernelGGL(label_gather_kernel, dim3(pp_stream_blocks(nq)), dim3(PP_THREADS), 0, s, (const int32_t*)idx, idx_capacity,
+  hipLaunchKernelGGL(label_units_kernel<true>, dim3(mt_stream_blocks(P.nunits, PP_WAVES)), dim3(PP_THREADS), 0, s, P);
+  hipLaunchKernelGGL(label_gather_kernel, dim3(mt_stream_blocks(nq, PP_THREADS)), dim3(PP_THREADS), 0, s, (const int32_t*)idx, idx_capacity,
                      (const int64_t*)P.base, nslots, qslot, qrank, nq, H, W, out);
   MT_CHECK_LAUNCH("label_locations");
   return MT_OK;

@@ -661,41 +661,57 @@ def downsample_seg_nearest(seg, out_spatial, remove_minus_one=False, out=None):
     return out
 
 
-CC_MAX_VOXELS = 2 ** 31 - 1      # mt_cc_*: int32 linear indices
+# ---- the data path: post-processing, cropping, training-case preprocessing, evaluation, dataset analysis -----------------------------
+MAX_VOXELS = 2 ** 31 - 1         # int32 linear indices and ranks in every kernel of the data path
+CC_MAX_VOXELS = CROP_MAX_VOXELS = LABEL_MAX_VOXELS = FG_MAX_VOXELS = MAX_VOXELS
+_CC, _CROP = "connected-component post-processing runs", "cropping to the non-zero region runs"
+_PRE, _EVAL, _AN = "training-case preprocessing runs", "the evaluation kernels run", "the dataset analysis kernels run"
 
 
-def cc_check_shape(shape):
-    """Shape rules of mt_cc_label3d / mt_cc_remove, checked on the shape alone (nothing is read or allocated)."""
+def _require_device(what, *tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("multitalent_amd: %s on a HIP device only; there is no CPU fallback" % what)
+
+
+def _volume_shape(shape, who, allow_empty):
+    """A [D, H, W] shape within the int32 index range of the device labelling, checked on the shape alone (nothing is read or
+    allocated).  who: "<unit>: <the volume that is expected>"."""
     shape = tuple(int(i) for i in shape)
-    if len(shape) != 3:
-        raise ValueError("connected components: a 3-D label volume [D, H, W] is expected, got shape %s" % (shape,))
-    if shape[0] * shape[1] * shape[2] > CC_MAX_VOXELS:
-        raise ValueError("connected components: %d voxels exceed the int32 index range of the device labelling"
-                         % (shape[0] * shape[1] * shape[2]))
+    if len(shape) != 3 or (not allow_empty and min(shape) < 1):
+        raise ValueError("%s is expected, got shape %s" % (who, shape))
+    if shape[0] * shape[1] * shape[2] > MAX_VOXELS:
+        raise ValueError("%s: %d voxels exceed the int32 index range of the device labelling"
+                         % (who.split(':')[0], shape[0] * shape[1] * shape[2]))
     return shape
 
 
-def _check_cc_dev(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError("multitalent_amd: connected-component post-processing runs on a HIP device only; there is no CPU fallback")
+def _member_table(member):
+    """256 host entries, non-zero = in the mask -> the byte table of the C ABI."""
+    tab = np.zeros(256, dtype=np.uint8)
+    tab[:] = np.asarray(member, dtype=bool).reshape(256)
+    return tab
+
+
+def cc_check_shape(shape):
+    """Shape rules of mt_cc_label3d / mt_cc_remove."""
+    return _volume_shape(shape, "connected components: a 3-D label volume [D, H, W]", True)
 
 
 def cc_label3d(seg, member, labels=None, sizes=None, stats=None):
     """seg: [D, H, W] uint8 device tensor (contiguous); member: 256 host entries, non-zero = in the mask.
     -> (labels, sizes, stats) int32 device tensors [D, H, W], [D, H, W], [2] (see mt_cc_label3d).  Nothing is synchronised."""
     D, H, W = cc_check_shape(seg.shape)
-    _check_cc_dev(seg)
+    _require_device(_CC, seg)
     assert seg.dtype == torch.uint8 and seg.is_contiguous()
-    tab = np.zeros(256, dtype=np.uint8)
-    tab[:] = np.asarray(member, dtype=bool).reshape(256)
+    tab = _member_table(member)
     if labels is None:
         labels = torch.empty((D, H, W), dtype=torch.int32, device=seg.device)
     if sizes is None:
         sizes = torch.empty((D, H, W), dtype=torch.int32, device=seg.device)
     if stats is None:
         stats = torch.empty(2, dtype=torch.int32, device=seg.device)
-    _check_cc_dev(labels, sizes, stats)
+    _require_device(_CC, labels, sizes, stats)
     _lib.check(_lib.load().mt_cc_label3d(_ptr(seg), D, H, W, tab.ctypes.data_as(C.c_void_p), _ptr(labels), _ptr(sizes), _ptr(stats),
                                          _stream()), 'cc_label3d')
     return labels, sizes, stats
@@ -705,7 +721,7 @@ def cc_remove(seg, labels, sizes, stats, volume_per_voxel, min_size=None, remove
     """In place on seg (uint8 device tensor [D, H, W]): zero every component of (labels, sizes, stats) from cc_label3d that
     the reference's rule removes (see mt_cc_remove).  -> `removed`, int32 device tensor [1]: the largest removed count."""
     D, H, W = cc_check_shape(seg.shape)
-    _check_cc_dev(seg, labels, sizes, stats)
+    _require_device(_CC, seg, labels, sizes, stats)
     assert seg.dtype == torch.uint8 and seg.is_contiguous()
     if removed is None:
         removed = torch.empty(1, dtype=torch.int32, device=seg.device)
@@ -715,30 +731,15 @@ def cc_remove(seg, labels, sizes, stats, volume_per_voxel, min_size=None, remove
     return removed
 
 
-CROP_MAX_VOXELS = CC_MAX_VOXELS  # mt_fill_holes3d / mt_crop_nonzero: int32 linear indices
-
-
 def crop_check_shape(shape):
-    """Shape rules of mt_fill_holes3d / mt_crop_nonzero for a [D, H, W] volume, checked on the shape alone."""
-    shape = tuple(int(i) for i in shape)
-    if len(shape) != 3 or min(shape) < 1:
-        raise ValueError("cropping: a non-empty 3-D volume [D, H, W] is expected, got shape %s" % (shape,))
-    if shape[0] * shape[1] * shape[2] > CROP_MAX_VOXELS:
-        raise ValueError("cropping: %d voxels exceed the int32 index range of the device labelling"
-                         % (shape[0] * shape[1] * shape[2]))
-    return shape
-
-
-def _check_crop_dev(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError("multitalent_amd: cropping to the non-zero region runs on a HIP device only; there is no CPU fallback")
+    """Shape rules of mt_fill_holes3d / mt_crop_nonzero for a [D, H, W] volume."""
+    return _volume_shape(shape, "cropping: a non-empty 3-D volume [D, H, W]", False)
 
 
 def nonzero_mask(data, mask=None):
     """data: [C, ...] float32 device tensor (contiguous) -> uint8 device tensor data.shape[1:]: 1 where any channel is != 0
     (numpy's rule on the bit pattern, see mt_nonzero_mask).  `mask` may have any alignment.  Nothing is synchronised."""
-    _check_crop_dev(data)
+    _require_device(_CROP, data)
     assert data.dtype == torch.float32 and data.is_contiguous() and data.dim() >= 2
     Cn = int(data.shape[0])
     V = int(data.numel()) // max(Cn, 1)
@@ -746,7 +747,7 @@ def nonzero_mask(data, mask=None):
         raise ValueError("nonzero_mask: empty input of shape %s" % (tuple(data.shape),))
     if mask is None:
         mask = torch.empty(tuple(data.shape[1:]), dtype=torch.uint8, device=data.device)
-    _check_crop_dev(mask)
+    _require_device(_CROP, mask)
     assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == V
     _lib.check(_lib.load().mt_nonzero_mask(_ptr(data), Cn, V, _ptr(mask), _stream()), 'nonzero_mask')
     return mask
@@ -757,14 +758,14 @@ def fill_holes3d(mask, bbox=None, ws=None):
     -> (mask, bbox): bbox int32 device tensor [7] = lo_d, hi_d, lo_h, hi_h, lo_w, hi_w (hi exclusive) and the number of set voxels
     (see mt_fill_holes3d).  ws: optional uint8 device scratch of at least fill_holes3d_workspace bytes.  Nothing is synchronised."""
     D, H, W = crop_check_shape(mask.shape)
-    _check_crop_dev(mask)
+    _require_device(_CROP, mask)
     assert mask.dtype == torch.uint8 and mask.is_contiguous()
     need = int(_lib.load().mt_fill_holes3d_workspace(D, H, W))
     if ws is None:
         ws = torch.empty(need, dtype=torch.uint8, device=mask.device)
     if bbox is None:
         bbox = torch.empty(7, dtype=torch.int32, device=mask.device)
-    _check_crop_dev(ws, bbox)
+    _require_device(_CROP, ws, bbox)
     assert bbox.dtype == torch.int32 and bbox.is_contiguous() and bbox.numel() == 7
     _lib.check(_lib.load().mt_fill_holes3d(_ptr(mask), D, H, W, _ptr(bbox), _ptr(ws), ws.numel() * ws.element_size(), _stream()),
                'fill_holes3d')
@@ -781,7 +782,7 @@ def crop_nonzero(data, mask, box, seg=None, nonzero_label=-1):
     ints lo_d, hi_d, lo_h, hi_h, lo_w, hi_w.  -> (data[:, box] bit for bit, seg): int8 [1, box] (0 inside the mask, nonzero_label
     outside) without `seg`, else float32 [CS, box] (see mt_crop_nonzero).  Nothing is synchronised."""
     D, H, W = crop_check_shape(mask.shape)
-    _check_crop_dev(data, mask)
+    _require_device(_CROP, data, mask)
     assert data.dtype == torch.float32 and data.is_contiguous() and data.dim() == 4 and tuple(data.shape[1:]) == (D, H, W)
     assert mask.dtype == torch.uint8 and mask.is_contiguous()
     b = np.ascontiguousarray(np.asarray(box, dtype=np.int64).reshape(6))
@@ -797,7 +798,7 @@ def crop_nonzero(data, mask, box, seg=None, nonzero_label=-1):
         seg_out = torch.empty((1,) + bs, dtype=torch.int8, device=data.device)
         seg_ptr, CS = None, 0
     else:
-        _check_crop_dev(seg)
+        _require_device(_CROP, seg)
         assert seg.dtype == torch.float32 and seg.is_contiguous() and seg.dim() == 4 and tuple(seg.shape[1:]) == (D, H, W)
         CS = int(seg.shape[0])
         seg_out = torch.empty((CS,) + bs, dtype=torch.float32, device=data.device)
@@ -809,21 +810,14 @@ def crop_nonzero(data, mask, box, seg=None, nonzero_label=-1):
 
 MOMENTS_ALL, MOMENTS_SEG_GE0, MOMENTS_OPEN_RANGE = 0, 1, 2
 MOMENTS_MAX_CHANNELS = 16
-LABEL_MAX_VOXELS = CC_MAX_VOXELS  # mt_label_counts / mt_label_locations: int32 linear indices
 LABEL_MAX_CLASSES = 255
-
-
-def _check_pre_dev(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError("multitalent_amd: training-case preprocessing runs on a HIP device only; there is no CPU fallback")
 
 
 def masked_moments(data, pred=MOMENTS_ALL, seg=None, lo=None, hi=None, stats=None):
     """data: [C, ...] float32 device tensor (contiguous).  -> stats, float64 device tensor [C, 3] = count, mean, population sd of
     every channel over the voxels the predicate selects: all of them, those with seg >= 0 (seg: float32, data.shape[1:]), or those
     with lo[c] < x < hi[c] (host values); see mt_masked_moments.  Deterministic; nothing is synchronised."""
-    _check_pre_dev(data)
+    _require_device(_PRE, data)
     assert data.dtype == torch.float32 and data.is_contiguous() and data.dim() >= 2
     Cn = int(data.shape[0])
     V = int(data.numel()) // max(Cn, 1)
@@ -831,7 +825,7 @@ def masked_moments(data, pred=MOMENTS_ALL, seg=None, lo=None, hi=None, stats=Non
         raise ValueError("masked_moments: 1..%d non-empty channels are expected, got shape %s" % (MOMENTS_MAX_CHANNELS, tuple(data.shape)))
     seg_ptr = lo_ptr = hi_ptr = None
     if pred == MOMENTS_SEG_GE0:
-        _check_pre_dev(seg)
+        _require_device(_PRE, seg)
         assert seg.dtype == torch.float32 and seg.is_contiguous() and seg.numel() == V
         seg_ptr = _ptr(seg)
     elif pred == MOMENTS_OPEN_RANGE:
@@ -844,7 +838,7 @@ def masked_moments(data, pred=MOMENTS_ALL, seg=None, lo=None, hi=None, stats=Non
     ws = torch.empty(int(lib.mt_masked_moments_workspace(Cn, V)), dtype=torch.uint8, device=data.device)
     if stats is None:
         stats = torch.empty((Cn, 3), dtype=torch.float64, device=data.device)
-    _check_pre_dev(stats)
+    _require_device(_PRE, stats)
     assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == Cn * 3
     _lib.check(lib.mt_masked_moments(_ptr(data), Cn, V, int(pred), seg_ptr, lo_ptr, hi_ptr, _ptr(stats), _ptr(ws), ws.numel(), _stream()),
                'masked_moments')
@@ -855,15 +849,15 @@ def intensity_normalize(x, clip=None, mean=0.0, sd=1.0, stats=None, eps=0.0, seg
     """In place on one channel x (float32 device tensor, contiguous): clip to `clip` = (lo, hi) when given, then
     (x - m) / (s + eps) in float32 with (m, s) = (mean, sd), or the (mean, sd) of `stats` (one float64 device triple of
     masked_moments); where `seg` (float32, same size) is not >= 0 the result is 0.  See mt_intensity_normalize."""
-    _check_pre_dev(x)
+    _require_device(_PRE, x)
     assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0
     seg_ptr = stats_ptr = None
     if seg is not None:
-        _check_pre_dev(seg)
+        _require_device(_PRE, seg)
         assert seg.dtype == torch.float32 and seg.is_contiguous() and seg.numel() == x.numel()
         seg_ptr = _ptr(seg)
     if stats is not None:
-        _check_pre_dev(stats)
+        _require_device(_PRE, stats)
         assert stats.dtype == torch.float64 and stats.numel() == 3 and stats.is_contiguous()
         stats_ptr = _ptr(stats)
     lo, hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
@@ -893,7 +887,7 @@ def label_counts(seg, all_classes):
         raise ValueError("label_counts: 1..%d distinct non-negative labels are expected, got %s" % (LABEL_MAX_CLASSES, classes))
     if any(c != f for c, f in zip(classes, all_classes)):
         raise ValueError("label_counts: labels must be integers, got %s" % (list(all_classes),))
-    _check_pre_dev(seg)
+    _require_device(_PRE, seg)
     assert seg.dtype == torch.float32 and seg.is_contiguous()
     tab = np.full(max(classes) + 1, 255, dtype=np.uint8)
     tab[classes] = np.arange(len(classes), dtype=np.uint8)
@@ -937,12 +931,6 @@ SD_MAX_AXIS = 32766             # mt_surface_distances: int16 site offsets
 SELECT_MAX_RANKS = 8
 
 
-def _check_eval_dev(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError("multitalent_amd: the evaluation kernels run on a HIP device only; there is no CPU fallback")
-
-
 def seg_joint_hist(test, ref, remap, num_classes, hist=None):
     """test, ref: contiguous uint8 device tensors of the same shape (any number of axes); remap: 256 host entries in
     0..num_classes-1.  -> hist, int64 device tensor [num_classes, num_classes]: hist[i, j] = #{v : remap[test[v]] == i and
@@ -956,13 +944,13 @@ def seg_joint_hist(test, ref, remap, num_classes, hist=None):
     if tab.min() < 0 or tab.max() >= Cn:
         raise ValueError("seg_joint_hist: remap entries must lie in 0..%d" % (Cn - 1))
     tab = np.ascontiguousarray(tab, dtype=np.uint8)
-    _check_eval_dev(test, ref)
+    _require_device(_EVAL, test, ref)
     assert test.dtype == torch.uint8 and ref.dtype == torch.uint8 and test.is_contiguous() and ref.is_contiguous()
     if test.numel() == 0:
         raise ValueError("seg_joint_hist: empty volume")
     if hist is None:
         hist = torch.empty((Cn, Cn), dtype=torch.int64, device=test.device)
-    _check_eval_dev(hist)
+    _require_device(_EVAL, hist)
     assert hist.dtype == torch.int64 and hist.is_contiguous() and hist.numel() == Cn * Cn
     _lib.check(_lib.load().mt_seg_joint_hist(_ptr(test), _ptr(ref), test.numel(), tab.ctypes.data_as(C.c_void_p), Cn, _ptr(hist),
                                              _stream()), 'seg_joint_hist')
@@ -992,10 +980,9 @@ def surface_distances(test, ref, member, spacing=None, connectivity=1, capacity=
         sp = np.ascontiguousarray(np.asarray(spacing, dtype=np.float64).reshape(-1))
         if sp.shape != (3,) or not np.all(np.isfinite(sp)) or not np.all(sp > 0):
             raise ValueError("surface distances: spacing must be three positive numbers (z, y, x), got %r" % (spacing,))
-    _check_eval_dev(test, ref)
+    _require_device(_EVAL, test, ref)
     assert test.dtype == torch.uint8 and ref.dtype == torch.uint8 and test.is_contiguous() and ref.is_contiguous()
-    tab = np.zeros(256, dtype=np.uint8)
-    tab[:] = np.asarray(member, dtype=bool).reshape(256)
+    tab = _member_table(member)
     if out is not None:
         capacity = out.numel()
     elif capacity is None:
@@ -1009,7 +996,7 @@ def surface_distances(test, ref, member, spacing=None, connectivity=1, capacity=
     need = lib.mt_surface_distances_workspace(D, H, W, capacity)
     if ws is None:
         ws = torch.empty(need, dtype=torch.uint8, device=test.device)
-    _check_eval_dev(out, stats, ws)
+    _require_device(_EVAL, out, stats, ws)
     assert out.dtype == torch.float64 and out.is_contiguous() and stats.dtype == torch.float64 and stats.numel() == 6
     _lib.check(lib.mt_surface_distances(_ptr(test), _ptr(ref), D, H, W, tab.ctypes.data_as(C.c_void_p),
                                         sp.ctypes.data_as(C.c_void_p) if sp is not None else C.c_void_p(0), int(connectivity),
@@ -1023,40 +1010,38 @@ def surface_distances_workspace(shape, capacity):
     return int(_lib.load().mt_surface_distances_workspace(D, H, W, max(1, int(capacity))))
 
 
-def select_kth(x, ranks, out=None, ws=None):
-    """x: 1-D contiguous fp64 device tensor of non-negative values; ranks: up to 8 host ints in 0..len(x)-1.
-    -> fp64 device tensor [len(ranks)]: the ranks[r]-th smallest of x (radix select, see mt_select_kth).  Nothing is synchronised."""
+def _select_kth(x, ranks, out, ws, dtype, name):
+    what = _EVAL if name == 'select_kth' else _AN        # the unit each entry point belongs to
     ranks = [int(r) for r in ranks]
     n = int(x.numel())
     if x.dim() != 1 or n < 1:
-        raise ValueError("select_kth: a non-empty 1-D tensor is expected, got shape %s" % (tuple(x.shape),))
+        raise ValueError("%s: a non-empty 1-D tensor is expected, got shape %s" % (name, tuple(x.shape)))
     if not 1 <= len(ranks) <= SELECT_MAX_RANKS:
-        raise ValueError("select_kth: %d ranks (1..%d)" % (len(ranks), SELECT_MAX_RANKS))
+        raise ValueError("%s: %d ranks (1..%d)" % (name, len(ranks), SELECT_MAX_RANKS))
     if min(ranks) < 0 or max(ranks) >= n:
-        raise ValueError("select_kth: ranks %s outside 0..%d" % (ranks, n - 1))
-    _check_eval_dev(x)
-    assert x.dtype == torch.float64 and x.is_contiguous()
+        raise ValueError("%s: ranks %s outside 0..%d" % (name, ranks, n - 1))
+    _require_device(what, x)
+    assert x.dtype == dtype and x.is_contiguous()
     lib = _lib.load()
     if out is None:
-        out = torch.empty(len(ranks), dtype=torch.float64, device=x.device)
+        out = torch.empty(len(ranks), dtype=dtype, device=x.device)
     if ws is None:
-        ws = torch.empty(lib.mt_select_kth_workspace(len(ranks)), dtype=torch.uint8, device=x.device)
-    _check_eval_dev(out, ws)
+        ws = torch.empty(getattr(lib, 'mt_%s_workspace' % name)(len(ranks)), dtype=torch.uint8, device=x.device)
+    _require_device(what, out, ws)
+    assert out.dtype == dtype and out.is_contiguous() and out.numel() >= len(ranks)
     rk = (C.c_long * len(ranks))(*ranks)
-    _lib.check(lib.mt_select_kth(_ptr(x), n, C.cast(rk, C.c_void_p), len(ranks), _ptr(out), _ptr(ws), ws.numel(), _stream()),
-               'select_kth')
+    _lib.check(getattr(lib, 'mt_' + name)(_ptr(x), n, C.cast(rk, C.c_void_p), len(ranks), _ptr(out), _ptr(ws), ws.numel(), _stream()), name)
     return out
 
 
-FG_MAX_VOXELS = CC_MAX_VOXELS     # mt_fg_sample_count / mt_fg_sample_gather: int32 ranks
+def select_kth(x, ranks, out=None, ws=None):
+    """x: 1-D contiguous fp64 device tensor; ranks: up to 8 host ints in 0..len(x)-1.  -> fp64 device tensor [len(ranks)]: the
+    ranks[r]-th smallest of x, an element of x (radix select on signed doubles, see mt_select_kth).  Nothing is synchronised."""
+    return _select_kth(x, ranks, out, ws, torch.float64, 'select_kth')
+
+
 FG_MAX_CHANNELS = 16
 LABEL_PRESENCE_MIN, LABEL_PRESENCE_MAX = -1, 1022
-
-
-def _check_an_dev(*ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError("multitalent_amd: the dataset analysis kernels run on a HIP device only; there is no CPU fallback")
 
 
 class FgIndex:
@@ -1081,7 +1066,7 @@ def fg_sample_count(seg):
         raise ValueError("fg_sample_count: an empty label map")
     if V > FG_MAX_VOXELS:
         raise ValueError("fg_sample_count: %d voxels exceed the int32 index range of the device compaction" % V)
-    _check_an_dev(seg)
+    _require_device(_AN, seg)
     assert seg.dtype == torch.float32 and seg.is_contiguous()
     lib = _lib.load()
     ws = torch.empty(int(lib.mt_fg_sample_workspace(V)), dtype=torch.uint8, device=seg.device)
@@ -1107,7 +1092,7 @@ def fg_sample(data, seg, stride=10, out=None, offset=0, index=None):
         raise ValueError("fg_sample: %d channels (1..%d)" % (Cn, FG_MAX_CHANNELS))
     if V < 1 or int(data.numel()) != Cn * V:
         raise ValueError("fg_sample: data %s and seg %s do not match" % (tuple(data.shape), tuple(seg.shape)))
-    _check_an_dev(data, seg)
+    _require_device(_AN, data, seg)
     assert data.dtype == torch.float32 and data.is_contiguous()
     if index is None:
         index = fg_sample_count(seg)
@@ -1120,7 +1105,7 @@ def fg_sample(data, seg, stride=10, out=None, offset=0, index=None):
         if offset != 0:
             raise ValueError("fg_sample: an offset needs `out`")
         out = torch.empty((Cn, m), dtype=torch.float32, device=data.device)
-    _check_an_dev(out)
+    _require_device(_AN, out)
     if out.dim() != 2 or int(out.shape[0]) != Cn or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError("fg_sample: out must be a contiguous float32 tensor [%d, capacity]" % Cn)
     cap = int(out.shape[1])
@@ -1138,27 +1123,7 @@ def select_kth_f32(x, ranks, out=None, ws=None):
     """x: 1-D contiguous float32 device tensor (any 4-byte aligned view); ranks: up to 8 host ints in 0..len(x)-1.
     -> float32 device tensor [len(ranks)]: the ranks[r]-th smallest of x, an element of x (radix select on signed floats, see
     mt_select_kth_f32).  Nothing is synchronised."""
-    ranks = [int(r) for r in ranks]
-    n = int(x.numel())
-    if x.dim() != 1 or n < 1:
-        raise ValueError("select_kth_f32: a non-empty 1-D tensor is expected, got shape %s" % (tuple(x.shape),))
-    if not 1 <= len(ranks) <= SELECT_MAX_RANKS:
-        raise ValueError("select_kth_f32: %d ranks (1..%d)" % (len(ranks), SELECT_MAX_RANKS))
-    if min(ranks) < 0 or max(ranks) >= n:
-        raise ValueError("select_kth_f32: ranks %s outside 0..%d" % (ranks, n - 1))
-    _check_an_dev(x)
-    assert x.dtype == torch.float32 and x.is_contiguous()
-    lib = _lib.load()
-    if out is None:
-        out = torch.empty(len(ranks), dtype=torch.float32, device=x.device)
-    if ws is None:
-        ws = torch.empty(lib.mt_select_kth_f32_workspace(len(ranks)), dtype=torch.uint8, device=x.device)
-    _check_an_dev(out, ws)
-    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= len(ranks)
-    rk = (C.c_long * len(ranks))(*ranks)
-    _lib.check(lib.mt_select_kth_f32(_ptr(x), n, C.cast(rk, C.c_void_p), len(ranks), _ptr(out), _ptr(ws), ws.numel(), _stream()),
-               'select_kth_f32')
-    return out
+    return _select_kth(x, ranks, out, ws, torch.float32, 'select_kth_f32')
 
 
 def label_presence(seg, what='label map'):
@@ -1168,7 +1133,7 @@ def label_presence(seg, what='label map'):
     V = int(seg.numel())
     if V < 1:
         raise ValueError("label_presence: %s is empty" % what)
-    _check_an_dev(seg)
+    _require_device(_AN, seg)
     assert seg.dtype == torch.float32 and seg.is_contiguous()
     buf = torch.empty(33, dtype=torch.int32, device=seg.device)
     _lib.check(_lib.load().mt_label_presence(_ptr(seg), V, _ptr(buf), C.c_void_p(buf.data_ptr() + 4 * 32), _stream()), 'label_presence')

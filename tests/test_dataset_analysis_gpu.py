@@ -1,4 +1,4 @@
-"""The dataset fingerprint on the device: the kernels of csrc/analyze.hip against numpy (bit for bit / `==`), `DatasetAnalyzer`
+"""The dataset fingerprint on the device: the kernels of csrc/analyze.hip and csrc/select.hip against numpy (bit for bit / `==`), `DatasetAnalyzer`
 against the REAL reference's (tools/oracle_gen/make_golden_dataset_analysis.py -> golden/dataset_analysis.npz), and the chain offline
 cropper -> analyzer -> GenericPreprocessor.run on files.
 Bounds against the golden: mn and mx equal; an interpolated value within 2 x dev64 + 1 float32 ulp of the value; mean and sd within
@@ -95,6 +95,23 @@ def test_fg_sample_float_predicate_nan_counts_slots_and_repeatability(dev):
         ops.fg_sample(dd, sd, 0)
     with pytest.raises(ValueError, match="channels"):
         ops.fg_sample(torch.zeros((17, 4), device=dev), torch.zeros(4, device=dev), 10)
+
+
+def test_fg_sample_over_more_units_than_scan_threads(dev):
+    """301 units of 8192 voxels, the last one 5 voxels long: every thread of the scan's workgroup owns up to two units, and the
+    threads beyond unit 300 none."""
+    from multitalent_amd import ops
+    rs = np.random.RandomState(11)
+    V = 8192 * 300 + 5
+    density = np.linspace(0.02, 0.9, V) * (np.arange(V) // 8192 % 7 != 3)    # rising along the volume, some units empty
+    seg = np.where(rs.rand(V) < density, rs.randint(1, 4, V), rs.randint(-1, 1, V)).astype(np.float32).reshape(1, 1, V)
+    seg[0, 0, -1] = 2
+    data = rs.randn(2, 1, 1, V).astype(np.float32)
+    dd, sd = torch.from_numpy(data).to(dev), torch.from_numpy(seg).to(dev)
+    for stride in (10, 1):
+        want = data[:, seg > 0][:, ::stride]
+        out, n, nans = ops.fg_sample(dd, sd, stride)
+        assert n == int((seg > 0).sum()) and np.array_equal(_bits(out.cpu().numpy()), _bits(want)) and nans.cpu().tolist() == [0, 0]
 
 
 # ---- select -------------------------------------------------------------------------------------------------------------------------

@@ -355,3 +355,71 @@ def test_select_kth(dev):
         assert np.array_equal(got, np.sort(x)[ranks]), n
     with pytest.raises(ValueError):
         ops.select_kth(torch.zeros(4, dtype=torch.float64, device=dev), [4])
+
+
+def _f64_value_sets(rng, n):
+    """Non-negative float64 inputs for the grouped radix select (8 passes of 8 bits on the uint64 key)."""
+    tiny = np.nextafter(1.0, 2.0)
+    return {'decades': np.abs(rng.standard_normal(n)) * 10.0 ** rng.integers(-3, 4, n),          # seven decades
+            'equal': np.full(n, 3.5),                                         # every rank in one group through all eight passes
+            'last_bit': np.where(rng.random(n) < 0.5, 1.0, tiny),             # the groups split in pass 7 only
+            'special': rng.choice(np.array([0.0, 5e-324, 1e-310, 1.0, np.inf]), n)}
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 8191, 8192, 8193, 300001])
+def test_select_kth_is_the_sorted_element(dev, n):
+    import torch
+    from multitalent_amd import ops
+    from multitalent_amd.experiment_planning.DatasetAnalyzer import _stat_ranks
+    ranks = _stat_ranks(n)
+    assert len(ranks) == 8
+    sets = _f64_value_sets(np.random.default_rng(n), n)
+    for name, x in sets.items():
+        assert x.dtype == np.float64 and not np.signbit(x).any()
+        xd = torch.from_numpy(x).to(dev)
+        got = ops.select_kth(xd, ranks).cpu().numpy()
+        again = ops.select_kth(xd, ranks).cpu().numpy()
+        assert got.dtype == np.float64 and np.array_equal(got, np.sort(x)[ranks]), (name, n, got)
+        assert got.tobytes() == again.tobytes()
+    some = [n - 1, 0, n // 3]                                                # fewer ranks, in any order
+    got = ops.select_kth(torch.from_numpy(sets['decades']).to(dev), some).cpu().numpy()
+    assert np.array_equal(got, np.sort(sets['decades'])[some])
+
+
+def test_select_kth_orders_signed_doubles(dev):
+    import torch
+    from multitalent_amd import ops
+    from multitalent_amd.experiment_planning.DatasetAnalyzer import _stat_ranks
+    rng = np.random.default_rng(5)
+    n = 8193
+    x = rng.standard_normal(n) * 10.0 ** rng.integers(-3, 4, n)
+    special = rng.choice(np.array([0.0, -0.0, 5e-324, -5e-324, np.inf, -np.inf, 1.0, -1.0]), n)
+    pick = rng.random(n) < 0.3
+    x[pick] = special[pick]
+    xd, srt = torch.from_numpy(x).to(dev), np.sort(x)
+    ranks = _stat_ranks(n)
+    got, want = ops.select_kth(xd, ranks).cpu().numpy(), srt[ranks]
+    assert (want < 0).any() and np.array_equal(got, want)
+    assert got[want != 0].tobytes() == want[want != 0].tobytes()
+    # np.sort leaves the order of -0.0 and +0.0 open; the key puts every -0.0 before every +0.0: the bit patterns at the edges
+    zeros = np.flatnonzero(srt == 0)
+    nneg = int((np.signbit(x) & (x == 0)).sum())
+    assert 0 < nneg < len(zeros)
+    edge = [int(zeros[0]), int(zeros[nneg - 1]), int(zeros[nneg]), int(zeros[-1])]
+    got = ops.select_kth(xd, edge).cpu().numpy()
+    assert got.view(np.uint64).tolist() == [1 << 63, 1 << 63, 0, 0]
+
+
+def test_select_kth_on_an_8_byte_aligned_view(dev):
+    import torch
+    from multitalent_amd import ops
+    from multitalent_amd.experiment_planning.DatasetAnalyzer import _stat_ranks
+    rng = np.random.default_rng(7)
+    for n in (1, 2, 5, 8193):
+        full = np.abs(rng.standard_normal(n + 4)) * 100.0 + 1.0
+        full[0] = 0.0
+        full[n + 1:] = 1e9                                                   # neighbours that would change every rank
+        view = torch.from_numpy(full).to(dev)[1:1 + n]
+        assert view.data_ptr() % 16 == 8
+        ranks = _stat_ranks(n)
+        assert np.array_equal(ops.select_kth(view, ranks).cpu().numpy(), np.sort(full[1:1 + n])[ranks])

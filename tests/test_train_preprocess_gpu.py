@@ -245,6 +245,26 @@ def test_label_locations_against_argwhere_256(dev):
     assert np.array_equal(out[:n], np.argwhere(seg == 300)) and (out[n:] == -1).all()
 
 
+def test_label_locations_over_more_units_than_scan_threads(dev):
+    """301 units of 8192 voxels, the last one 5 voxels long: every thread of the scan's workgroup owns up to two units, and the
+    threads beyond unit 300 none."""
+    from multitalent_amd import ops
+    rs = np.random.RandomState(12)
+    V = 8192 * 300 + 5
+    density = np.linspace(0.02, 0.9, V) * (np.arange(V) // 8192 % 7 != 3)    # rising along the volume, some units empty
+    seg = np.where(rs.rand(V) < density, rs.randint(1, 4, V), rs.randint(-1, 1, V)).astype(np.float32).reshape(1, 1, V)
+    seg[0, 0, -1] = 2
+    all_classes = [2, 3, 1]
+    counts, index = ops.label_counts(torch.from_numpy(seg).to(dev), all_classes)
+    want_counts = [int((seg == c).sum()) for c in all_classes]
+    assert counts.cpu().tolist() == want_counts and min(want_counts) > 100000
+    for slot, c in enumerate(all_classes):
+        locs = np.argwhere(seg == c)
+        rank = np.unique(np.concatenate([np.arange(0, len(locs), 7), [len(locs) - 1]]))
+        out = ops.label_locations(index, np.full(len(rank), slot, dtype=np.int32), rank, total=sum(want_counts)).cpu().numpy()
+        assert np.array_equal(out, locs[rank]), c
+
+
 def test_label_counts_rejects_bad_arguments(dev):
     from multitalent_amd import ops
     seg = torch.zeros((4, 4, 4), device=dev)
