@@ -418,6 +418,25 @@ int mt_affine_sample(const float* src, int N, int C, int D, int H, int W, float*
 int mt_resample_classify(const float* probs, int C, int D, int H, int W, int OD, int OH, int OW, int sep_axis,
                          const int32_t* class_order, int use_regions, uint8_t* out, long FD, long FH, long FW,
                          int bD, int bH, int bW, mt_stream_t stream);
+/* Ensemble merge (inference/ensemble_predictions.py:25-53 merge_files, evaluation/model_selection/ensemble.py:26-40 merge):
+ * `np.mean(np.vstack([np.load(f)['softmax'][None] for f in files]), 0)` -> argmax, or the region thresholds in
+ * regions_class_order -> re-insertion into the uncropped volume, in ONE streaming pass over the K members.
+ * members: HOST array of K device pointers (1 <= K <= MT_ENSEMBLE_MAX_MEMBERS; they travel to the kernel by value), each to
+ * float16 probabilities [C][chan_stride] of a D x H x W box, chan_stride >= V = D*H*W, 1 <= C <= 255.
+ * Arithmetic = numpy's float16 mean, bit for bit: float32 accumulation in member order ((m0 + m1) + m2) + ..., ONE IEEE float32
+ * division by (float)K, ONE round-to-nearest-even to float16, float16 subnormals kept.  The label is decided on that ROUNDED
+ * float16 mean: argmax with the first maximum winning, or (use_regions) the last channel i with mean_i > 0.5 gives
+ * class_order[i] (DEVICE int32[C], as in mt_resample_classify), else 0.  NaN members are outside the contract (the label of such
+ * a voxel is unspecified; the stored mean is still numpy's).
+ * out: uint8 [FD][FH][FW]; the box is written at offset (bD, bH, bW), which must lie inside the volume, clipped to the volume;
+ * voxels outside the box are not touched.  mean: NULL, or float16 [C][mean_stride], mean_stride >= V (only the V voxels of each
+ * channel are written).  Where the member pointers, mean, chan_stride and mean_stride are multiples of 8 elements every lane
+ * moves 16 bytes; any other alignment (2-byte) is served element by element.
+ * Traffic: 2*K*C*V bytes read, V written, + 2*C*V when the mean is kept. */
+#define MT_ENSEMBLE_MAX_MEMBERS 16
+int mt_ensemble_classify(const void* const* members, int K, int C, int D, int H, int W, long chan_stride,
+                         const int32_t* class_order, int use_regions, uint8_t* out, long FD, long FH, long FW,
+                         int bD, int bH, int bW, void* mean, long mean_stride, mt_stream_t stream);
 /* Connected-component post-processing (remove_all_but_the_largest_connected_component, postprocessing/connected_components.py:48-101).
  * mt_cc_label3d: `lmap, num_objects = scipy.ndimage.label(mask)` (:76) with scipy's default 3-D structure, 6-connectivity (face
  * neighbours only), on the mask {v : member[seg[v]] != 0} of a contiguous uint8 volume seg[D, H, W].  member: HOST array of 256

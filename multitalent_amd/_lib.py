@@ -122,6 +122,7 @@ SIGNATURES = {
     'mt_spline_prefilter3': (_i, [_vp, _i, _i, _i, _i, _i, _vp]),
     'mt_affine_sample': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _f, _i, _vp]),
     'mt_resample_classify': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _l, _l, _l, _i, _i, _i, _vp]),
+    'mt_ensemble_classify': (_i, [_P(_vp), _i, _i, _i, _i, _i, _l, _vp, _i, _vp, _l, _l, _l, _i, _i, _i, _vp, _l, _vp]),
     'mt_cc_label3d': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'mt_cc_remove': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _i, _d, _vp, _vp]),
     'mt_nonzero_mask': (_i, [_vp, _i, _l, _vp, _vp]),
