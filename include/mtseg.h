@@ -574,6 +574,34 @@ size_t mt_select_kth_f32_workspace(int nranks);
 int mt_select_kth_f32(const float* x, long n, const long* ranks /* host */, int nranks, float* out, void* ws, size_t ws_bytes,
                       mt_stream_t stream);
 int mt_label_presence(const float* seg, long V, uint32_t* bitmap, int32_t* flag, mt_stream_t stream);
+/* Training batches from cases kept on the device (training/dataloading/device_loading.py).  Additions to ABI 4.
+ * mt_patch_gather: the crop and np.pad of DataLoader3D.generate_train_batch (dataset_loading.py:338-372; the box arithmetic of
+ *   :259-336 stays on the host) for n <= MT_PATCH_MAX_SRC samples in ONE launch.  srcs: HOST array of n descriptors, passed to the
+ *   kernel by value (no device table, no copy, nothing to keep alive but the sources themselves).  Sample j has its own source: data
+ *   [C][sx, sy, sz] float32 and seg [sx, sy, sz] int16 (mt_seg_narrow), both on the device, of its own shape (a whole case, or a
+ *   staged sub-box of one), and the lower corner lb of its patch in source coordinates, which may be negative.  Output voxel
+ *   (j, c, d, h, w) of data_out [n, C, PD, PH, PW] reads source voxel lb + (d, h, w); outside the source it is 0 (MT_PAD_CONSTANT)
+ *   or the source voxel with every coordinate clamped (MT_PAD_EDGE): np.pad's meaning for the intersection of patch and source.
+ *   seg_out [n, 1, PD, PH, PW] is float32 and gets seg_fill (the loader passes -1) outside the source in either mode.  A copy: bit
+ *   for bit, NaN payloads included.  data_out / seg_out need 4-byte alignment only.  A thread owns 4 consecutive w; HBM-bound at
+ *   (4C + 2) bytes read and 4(C + 1) written per patch voxel.  n outside 1..16, an empty axis or a patch above INT32_MAX voxels is
+ *   MT_EINVAL before any launch.
+ * mt_seg_narrow: out[v] (int16, 8-byte aligned) = seg[v] for the float32 label map seg[V] (dataset_loading.py:338: the last channel
+ *   of a case, small integers, -1 outside the non-zero mask).  *flag (device int32) is SET to 1 when some value is non-integral,
+ *   NaN or outside int16, which is what makes the 16-bit storage lossless rather than assumed; it is never cleared by the call,
+ *   so one zeroed flag can watch several calls. */
+#define MT_PATCH_MAX_SRC 16
+#define MT_PAD_CONSTANT 0
+#define MT_PAD_EDGE 1
+typedef struct {
+  const float* data;   /* [C, sx, sy, sz] float32, device */
+  const int16_t* seg;  /* [sx, sy, sz] labels, device */
+  int32_t shape[3];    /* sx, sy, sz of THIS source */
+  int32_t lb[3];       /* lower corner of the patch in source coordinates; may be negative */
+} mt_patch_src_t;
+int mt_patch_gather(const mt_patch_src_t* srcs /* host, n <= MT_PATCH_MAX_SRC */, int n, int C, int PD, int PH, int PW, int pad_mode,
+                    float seg_fill, float* data_out, float* seg_out, mt_stream_t stream);
+int mt_seg_narrow(const float* seg, long V, int16_t* out, int32_t* flag, mt_stream_t stream);
 /* ---- device-side target preparation ----------------------------------------
  * Deep-supervision label pyramid: DownsampleSegForDSTransform2 / downsample_seg_for_ds_transform2 (downsampling.py:70-104,
  * order 0 = nearest through batchgenerators' resize_segmentation -> skimage.transform.resize(order 0, mode "edge") ->

@@ -56,7 +56,13 @@ class mt_pointwise_t(C.Structure):
                 ('stats_part', C.c_void_p), ('odtype', C.c_int32), ('scatter', C.c_int32), ('mma', C.c_int32)]
 
 
+class mt_patch_src_t(C.Structure):
+    _fields_ = [('data', C.c_void_p), ('seg', C.c_void_p), ('shape', C.c_int32 * 3), ('lb', C.c_int32 * 3)]
+
+
 MT_F32, MT_BF16, MT_F16 = 0, 1, 2
+MT_PATCH_MAX_SRC = 16
+MT_PAD_CONSTANT, MT_PAD_EDGE = 0, 1
 MT_ABI_VERSION = 4
 
 _vp, _i, _l, _f, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
@@ -146,6 +152,8 @@ SIGNATURES = {
     'mt_select_kth_f32_workspace': (_sz, [_i]),
     'mt_select_kth_f32': (_i, [_vp, _l, _vp, _i, _vp, _vp, _sz, _vp]),
     'mt_label_presence': (_i, [_vp, _l, _vp, _vp, _vp]),
+    'mt_patch_gather': (_i, [_P(mt_patch_src_t), _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    'mt_seg_narrow': (_i, [_vp, _l, _vp, _vp, _vp]),
     'mt_head_flip_accumulate': (_i, [_P(mt_pointwise_t), _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
     'mt_head_mirror_accumulate': (_i, [_P(mt_pointwise_t), _i, _i, _vp, _i, _f, _vp, _vp, _vp, _l, _l, _l, _i, _i, _i, _vp]),
     'mt_extract_tiles': (_i, [_vp, _i, _l, _l, _l, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -1145,5 +1145,62 @@ def label_presence(seg, what='label map'):
     return [int(b) - 1 for b in np.flatnonzero(bits)]
 
 
+_LOAD = "the patch gather of the device loader runs"
+PAD_MODES = {'constant': _lib.MT_PAD_CONSTANT, 'edge': _lib.MT_PAD_EDGE}
+
+
+def seg_narrow(seg, flag, out=None):
+    """seg: contiguous float32 device tensor of integer labels -> the same labels as int16 (`out`, or a new tensor of seg's shape).
+    flag: int32 device tensor of one element that the call sets to 1 when a value is not an integer of int16; the caller zeroes
+    and reads it (one flag can watch several calls).  Nothing is synchronised.  See mt_seg_narrow."""
+    _require_device(_LOAD, seg, flag)
+    assert seg.dtype == torch.float32 and seg.is_contiguous() and flag.dtype == torch.int32 and flag.numel() >= 1
+    if out is None:
+        out = torch.empty(seg.shape, dtype=torch.int16, device=seg.device)
+    assert out.dtype == torch.int16 and out.is_contiguous() and out.numel() == seg.numel() and out.is_cuda
+    if seg.numel():
+        _lib.check(_lib.load().mt_seg_narrow(_ptr(seg), int(seg.numel()), _ptr(out), _ptr(flag), _stream()), 'seg_narrow')
+    return out
+
+
+def patch_gather(sources, patch_size, pad_mode, data_out=None, seg_out=None, seg_fill=-1.0):
+    """sources: per sample (data [C, sx, sy, sz] float32, seg [sx, sy, sz] int16, lb) with contiguous device tensors and the lower
+    corner lb of the patch in that source's coordinates (may be negative).  -> (data [B, C, *patch] float32, seg [B, 1, *patch]
+    float32): np.pad(crop, pad_mode) of the data (`constant` = 0, or `edge`) and the labels padded with seg_fill, bit for bit.
+    One launch per MT_PATCH_MAX_SRC samples; nothing is synchronised.  data_out / seg_out: contiguous float32 device tensors of
+    those shapes to write into.  See mt_patch_gather."""
+    B, (PD, PH, PW) = len(sources), (int(i) for i in patch_size)
+    if B < 1:
+        raise ValueError("patch_gather: no samples")
+    Cn = int(sources[0][0].shape[0])
+    dev = sources[0][0].device
+    descs = (_lib.mt_patch_src_t * B)()
+    for j, (data, seg, lb) in enumerate(sources):
+        _require_device(_LOAD, data, seg)
+        if data.dtype != torch.float32 or seg.dtype != torch.int16 or not data.is_contiguous() or not seg.is_contiguous() \
+                or data.dim() != 4 or data.shape[0] != Cn or tuple(data.shape[1:]) != tuple(seg.shape) or data.device != dev:
+            raise ValueError("patch_gather: sample %d: data float32 [%d, x, y, z] and seg int16 [x, y, z], contiguous, on one device, "
+                             "are expected; got %s %s and %s %s" % (j, Cn, data.dtype, tuple(data.shape), seg.dtype, tuple(seg.shape)))
+        descs[j].data, descs[j].seg = data.data_ptr(), seg.data_ptr()
+        for a in range(3):
+            descs[j].shape[a], descs[j].lb[a] = int(seg.shape[a]), int(lb[a])
+    if data_out is None:
+        data_out = torch.empty((B, Cn, PD, PH, PW), dtype=torch.float32, device=dev)
+    if seg_out is None:
+        seg_out = torch.empty((B, 1, PD, PH, PW), dtype=torch.float32, device=dev)
+    _require_device(_LOAD, data_out, seg_out)
+    assert data_out.dtype == seg_out.dtype == torch.float32 and data_out.is_contiguous() and seg_out.is_contiguous()
+    assert tuple(data_out.shape) == (B, Cn, PD, PH, PW) and tuple(seg_out.shape) == (B, 1, PD, PH, PW)
+    lib, PV = _lib.load(), PD * PH * PW
+    with torch.cuda.device(dev):
+        for j0 in range(0, B, _lib.MT_PATCH_MAX_SRC):
+            n = min(_lib.MT_PATCH_MAX_SRC, B - j0)
+            part = C.cast(C.byref(descs, j0 * C.sizeof(_lib.mt_patch_src_t)), C.POINTER(_lib.mt_patch_src_t))
+            _lib.check(lib.mt_patch_gather(part, n, Cn, PD, PH, PW, PAD_MODES[pad_mode], float(seg_fill),
+                                           C.c_void_p(data_out.data_ptr() + 4 * j0 * Cn * PV), C.c_void_p(seg_out.data_ptr() + 4 * j0 * PV),
+                                           _stream()), 'patch_gather')
+    return data_out, seg_out
+
+
 _parse_select_env()
 _select_env = _select

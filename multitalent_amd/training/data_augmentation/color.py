@@ -216,8 +216,11 @@ class MoreDADeviceAugmenter:
 
     def __next__(self):
         b = next(self.loader)
-        data = torch.from_numpy(b['data']).to(self.device, non_blocking=True)
-        seg = torch.from_numpy(b['seg'][:, :1]).to(self.device, non_blocking=True)
+        if torch.is_tensor(b['data']):                      # DeviceDataLoader3D: the batch is on the device already
+            data, seg = b['data'].to(self.device), b['seg'][:, :1].to(self.device)
+        else:
+            data = torch.from_numpy(b['data']).to(self.device, non_blocking=True)
+            seg = torch.from_numpy(b['seg'][:, :1]).to(self.device, non_blocking=True)
         data, seg = self.spatial(data, seg)
         for t in self.color:
             data = t(data)

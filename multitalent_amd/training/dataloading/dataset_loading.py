@@ -12,7 +12,8 @@ Format (written by the reference's preprocessing, read here unchanged): `<case>.
 The sampler consumes numpy's GLOBAL random stream in exactly the reference's call order (one `choice` for the keys of a batch;
 per sample either three `randint` or `choice(class)` + `choice(voxel)`), so a seeded run reproduces the reference's batches bit
 for bit — that is how `tests/test_dataset_loading.py` pins it against `tests/golden/loader.npz`.
-Host-side component: numpy only, no device work (the device takes over at `DeviceBatchFeeder`)."""
+Host-side component: numpy only, no device work (the device takes over at `DeviceBatchFeeder`); `device_loading.py` is the same
+loader with the cases kept on the device."""
 import os
 import pickle
 from collections import OrderedDict
@@ -201,6 +202,7 @@ class SegToTargetGenerator:
         data, seg = b['data'], b['seg']
         if self.final_patch_size is not None and tuple(data.shape[2:]) != self.final_patch_size:
             sl = tuple(slice((s - f) // 2, (s - f) // 2 + f) for s, f in zip(data.shape[2:], self.final_patch_size))
-            data = np.ascontiguousarray(data[(slice(None), slice(None)) + sl])
-            seg = np.ascontiguousarray(seg[(slice(None), slice(None)) + sl])
+            contiguous = np.ascontiguousarray if isinstance(data, np.ndarray) else (lambda t: t.contiguous())   # device batches
+            data = contiguous(data[(slice(None), slice(None)) + sl])
+            seg = contiguous(seg[(slice(None), slice(None)) + sl])
         return {'data': data, 'target': seg[:, :1], 'properties': b['properties'], 'keys': b['keys']}

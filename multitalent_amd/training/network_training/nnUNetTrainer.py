@@ -660,17 +660,28 @@ class nnUNetTrainerV2(nnUNetTrainer):
 
     def get_basic_generators(self):
         """nnUNetTrainer.py:394-409 (MultiTalent: …_Trainer_DDP.py:625-661).  The loader draws network-sized patches: the
-        oversized `basic_generator_patch_size` only exists for the CPU SpatialTransform, which is not part of this path."""
+        oversized `basic_generator_patch_size` only exists for the CPU SpatialTransform, which is not part of this path.
+        With a HIP device and `device_dataloading` both loaders are DeviceDataLoader3D over ONE case cache (same draws, same
+        batches, as device tensors); without a device, or with the attribute off, they are the host DataLoader3D."""
         from ..dataloading.dataset_loading import DataLoader3D
         self.load_dataset()
         self.do_split()
         ps = tuple(int(i) for i in self.patch_size)
         bps = tuple(int(i) for i in self.basic_generator_patch_size) if self.device_augmentation else ps
-        mk = lambda ds, p: DataLoader3D(ds, p, ps, self.batch_size, False, oversample_foreground_percent=self.oversample_foreground_percent,
-                                        pad_mode="constant", pad_sides=self.pad_all_sides, memmap_mode='r',
-                                        sampling_probabilities=self._sampling_probabilities(list(ds.keys())))
+        cls, extra = DataLoader3D, {}
+        if self.device_dataloading and torch.cuda.is_available():
+            from ..dataloading.device_loading import DeviceCaseCache, DeviceDataLoader3D
+            dev = torch.device('cuda', torch.cuda.current_device())
+            budget = int(self.device_case_cache_fraction * torch.cuda.get_device_properties(dev).total_memory)
+            cls, extra = DeviceDataLoader3D, {'cache': DeviceCaseCache(dev, budget)}
+        mk = lambda ds, p: cls(ds, p, ps, self.batch_size, False, oversample_foreground_percent=self.oversample_foreground_percent,
+                               pad_mode="constant", pad_sides=self.pad_all_sides, memmap_mode='r',
+                               sampling_probabilities=self._sampling_probabilities(list(ds.keys())), **extra)
         return mk(self.dataset_tr, bps), mk(self.dataset_val, ps)
 
+    device_dataloading = True       # preprocessed cases resident on the device, batches by one gather launch (device_loading.py)
+    # share of the device's TOTAL memory the resident cases may take (the engine allocates lazily: free memory at set-up says nothing)
+    device_case_cache_fraction = 0.25
     device_augmentation = True      # rotation/scaling/intensity/mirror augmentation of the training batches on the device
 
     def setup_augmentation_params(self):
