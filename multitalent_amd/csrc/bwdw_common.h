@@ -1,9 +1,44 @@
-// Parameter blocks shared by the convolution translation units (conv_lds.hip plans, dispatches and reduces; bwdw_tr16.hip holds one
-// kernel family of the mixed-precision mode).
+// Parameter blocks and host helpers shared by the convolution translation units: conv_lds.hip (forward, backward-data, weight packing),
+// conv_bwdw.hip (backward-weight: plans, the one dispatch decision, the reduce), and the single-family units bwdw_tr16.hip and conv_x16.hip,
+// whose launchers are declared here and whose dispatch stays with the caller.
 #pragma once
 #include "mt_common.h"
 
 struct ConvChunk { short src, c0, ck, cglob; };
+
+// Split the concatenated input channels (C0 | C1) into chunks of <= ck channels that never straddle
+// the two sources.  Shared by packing and kernels so the packed order always matches.
+static inline int mt_build_chunks(int C0, int C1, int ck, ConvChunk* out) {
+  int n = 0;
+  const int Cs[2] = {C0, C1};
+  int cglob = 0;
+  for (int s = 0; s < 2; ++s) {
+    for (int c0 = 0; c0 < Cs[s]; c0 += ck) {
+      if (n >= MT_MAX_CHUNKS) return -1;
+      const int k = (Cs[s] - c0 < ck) ? (Cs[s] - c0) : ck;
+      out[n].src = (short)s; out[n].c0 = (short)c0; out[n].ck = (short)k; out[n].cglob = (short)(cglob + c0);
+      ++n;
+    }
+    cglob += Cs[s];
+  }
+  return n;
+}
+// 2 when every source can be staged as channel pairs (one 8 / 4-byte load: even channel count and stride, aligned base), else 1
+static inline int conv_fast_vec(const mt_conv3d_t* p) {
+  for (int i = 0; i < p->nsrc; ++i) {
+    const mt_src_t& s = p->src[i];
+    if ((s.cs & 1) || (s.C & 1) || (((uintptr_t)s.ptr) & (mt_is16(s.dtype) ? 3 : 7))) return 1;   // a channel pair = one 8 / 4-byte load
+  }
+  return 2;
+}
+// storage type of a problem's sources: their common type (-1: mixed or unknown)
+static inline int conv_src_dtype(const mt_conv3d_t* p) {
+  const int d = p->src[0].dtype;
+  if (p->nsrc == 2 && p->src[1].dtype != d) return -1;
+  return mt_dtype_ok(d) ? d : -1;
+}
+// a 2-bit MT_SEL_* field of p->select: 0 off, 1 the library's policy, 2 forced
+static inline int mt_sel3(const mt_conv3d_t* p, int shift) { const unsigned v = MT_SEL_GET(p->select, shift); return v == MT_SEL_OFF ? 0 : v == MT_SEL_FORCE ? 2 : 1; }
 
 struct ConvKParams {
   mt_conv3d_t c;

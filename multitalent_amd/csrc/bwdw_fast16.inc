@@ -268,8 +268,7 @@ __global__ __launch_bounds__(256) void conv_bwdw_fast16_kernel(const BwdWParams 
 }
 
 static bool bwdw_fast16_ok(const mt_conv3d_t* p, const mt_src_t* y) {
-  constexpr int use = 1;
-  if (!use || p->mma != 1 || y == nullptr) return false;
+  if (p->mma != 1 || y == nullptr) return false;
   const int xs = p->src[0].dtype;
   if (!(xs == MT_F16 || xs == MT_BF16)) return false;
   for (int i = 0; i < p->nsrc; ++i) {
@@ -289,15 +288,7 @@ static int launch_bwdw_fast16(const BwdWParams& P, hipStream_t st) {
   MT_REQUIRE(ldsb <= 160 * 1024, "bwd_weight: LDS tile too large (%zu)", ldsb);
   dim3 grid(P.nsg, mt_cdiv(P.ncot, P.cw), P.nchunks);
   const int xs = P.c.src[0].dtype, ys = P.y.dtype;
-#define MT_BW16_K(KFN_)                                                                                       \
-  do {                                                                                                        \
-    auto kfn = KFN_;                                                                                          \
-    if (ldsb > 64 * 1024) {                                                                                   \
-      hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb); \
-      if (e != hipSuccess) { mt_set_error("bwd_weight: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return MT_EHIP; } \
-    }                                                                                                         \
-    hipLaunchKernelGGL(kfn, grid, dim3(256), ldsb, st, P);                                                    \
-  } while (0)
+#define MT_BW16_K(KFN_) MT_BWDW_LAUNCH(KFN_, grid, ldsb, st, P)
 #define MT_BW16(TH_, TW_)                                                                                     \
   do {                                                                                                        \
     if (xs == MT_F16 && ys == MT_BF16) MT_BW16_K((conv_bwdw_fast16_kernel<KD, KH, KW, SD, SH, SW, TH_, TW_, MT_F16, MT_BF16>)); \
@@ -593,8 +584,7 @@ static bool bwdw_march16_geo(const mt_conv3d_t* p) {       // (the plan needs it
          p->Wo > 16 && p->Do >= 3;
 }
 static bool bwdw_march16_ok(const mt_conv3d_t* p, const mt_src_t* y) {
-  constexpr int use = 1;
-  return use && bwdw_fast16_ok(p, y) && p->src[0].dtype == MT_F16 && y->dtype == MT_BF16 && bwdw_march16_geo(p);
+  return bwdw_fast16_ok(p, y) && p->src[0].dtype == MT_F16 && y->dtype == MT_BF16 && bwdw_march16_geo(p);
 }
 template <int SD>
 static int launch_bwdw_march16(const BwdWParams& P, hipStream_t st) {
@@ -603,13 +593,7 @@ static int launch_bwdw_march16(const BwdWParams& P, hipStream_t st) {
   if (ldsb < BW_RED_LDS(27)) ldsb = BW_RED_LDS(27);
   dim3 grid(P.nsg, mt_cdiv(P.ncot, P.cw), P.nchunks);
   const int xs = P.c.src[0].dtype, ys = P.y.dtype;
-#define MT_BM16_K(KFN_)                                                                                       \
-  do {                                                                                                        \
-    auto kfn = KFN_;                                                                                          \
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb); \
-    if (e != hipSuccess) { mt_set_error("bwd_weight: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return MT_EHIP; } \
-    hipLaunchKernelGGL(kfn, grid, dim3(256), ldsb, st, P);                                                    \
-  } while (0)
+#define MT_BM16_K(KFN_) MT_BWDW_LAUNCH(KFN_, grid, ldsb, st, P)       // (110 KiB: always above the default)
   if (xs == MT_F16 && ys == MT_BF16) {
     if (P.cw == 4) MT_BM16_K((conv_bwdw_march16_kernel<SD, MT_F16, MT_BF16, 4>));
     else if (P.cw == 2) MT_BM16_K((conv_bwdw_march16_kernel<SD, MT_F16, MT_BF16, 2>));

@@ -1,5 +1,5 @@
 // bwdw_gemm.inc — backward-weight of the LOW-RESOLUTION convolutions in mixed precision (mt_conv3d_t.mma == 1) as im2col + one GEMM
-// with bf16 products (included by conv_lds.hip).
+// with bf16 products (included by conv_bwdw.hip).
 //
 // dW[tap][ci][co] = sum over output voxels o of act(X)[o*S + tap - P][ci] * dY[o][co]  (autograd of nn.Conv3d weights; reference ops
 // conv_blocks.py:116-213, generic_UNet.py:57,67) is a GEMM whose contraction index is the VOXEL: C[m = (tap, ci)][n = co] = A[m][k] B[n][k].
@@ -150,8 +150,7 @@ __global__ __launch_bounds__(256) void bwdw_gemm_kernel(const BgParams P) {
 // eligibility: mixed precision, stride-1 3x3x3 / 1x3x3 convolutions whose output rows are too short for the Winograd marching kernels
 // (W <= 16), contraction and operands small enough to stay in L2 (A <= 96 MB)
 static bool bwdw_use_gemm(const mt_conv3d_t* p, const mt_src_t* y) {
-  constexpr int use = 1;
-  if (!use || p->mma != 1 || y == nullptr) return false;
+  if (p->mma != 1 || y == nullptr) return false;
   if (!(p->dilD == 1 && p->dilH == 1 && p->dilW == 1 && p->SD == 1 && p->SH == 1 && p->SW == 1 && p->KH == 3 && p->KW == 3 && (p->KD == 3 || p->KD == 1))) return false;
   if (p->Wo > 16 || p->Cin < 16 || p->Cout < 16) return false;
   const double V = (double)p->N * p->Do * p->Ho * p->Wo;

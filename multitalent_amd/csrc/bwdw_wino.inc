@@ -1,4 +1,4 @@
-// bwdw_wino.inc — backward-weight of 3x3x3 stride-1 convolutions with a 2D Winograd transform (included by conv_lds.hip).
+// bwdw_wino.inc — backward-weight of 3x3x3 stride-1 convolutions with a 2D Winograd transform (included by conv_bwdw.hip).
 //
 // dW[kd][kh][kw] = sum over output voxels of X[o + k - 1] * dY[o].  Group the outputs of a plane into 2x2 (h, w) tiles: per tile
 // the (kh, kw) part is F(3x3, 2x2) — 3x3 results from a 4x4 X block and the 2x2 dY block with 16 instead of 36 products:

@@ -59,7 +59,7 @@ extern "C" int mt_inorm_finalize(const float* part, int N, int nsb, int C, doubl
 // workgroups of 256 threads on 256 CUs — 2.9 TB/s where the full-resolution launches reach 5.4 — so smaller tensors get
 // proportionally smaller blocks (>= 128 voxels, about 512 blocks per sample).
 #ifndef MT_VB_BLOCKS
-#define MT_VB_BLOCKS 512      // target workgroups per sample below full resolution (256 / 1024 measured no better: tools/build_norm_variant.sh)
+#define MT_VB_BLOCKS 512      // target workgroups per sample below full resolution (256 / 1024 measured no better: make variant UNIT=norm)
 #endif
 #ifndef MT_VB_MIN
 #define MT_VB_MIN 32

@@ -1,4 +1,4 @@
-# where does conv_tapsplit_kernel's time go?  ablation variants (tools/build_conv_variant.sh tsablN -DTS_ABL=N) on the low-resolution layers
+# where does conv_tapsplit_kernel's time go?  ablation variants (make -C multitalent_amd/csrc variant NAME=tsablN UNIT=conv_lds EXTRA=-DTS_ABL=N) on the low-resolution layers
 cd $GRAFT_REPO_ROOT
 for v in "" tsabl1 tsabl2 tsabl4 tsabl7; do
   [ -n "$v" ] && export MT_LIB_VARIANT=libmtseg_hip_$v.so

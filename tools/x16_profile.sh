@@ -1,6 +1,7 @@
 #!/bin/bash
 # conv_x16_kernel / conv_bf16_kernel: where the cycles go.  Needs the variant libraries built by
-#   for a in 7 12 4 3 35; do tools/build_x16_variant.sh abl$a -DX16_ABL=$a; done; tools/build_x16_variant.sh ts -DX16_TS=1
+#   for a in 7 12 4 3 35; do make -C multitalent_amd/csrc variant NAME=abl$a UNIT=conv_x16 EXTRA=-DX16_ABL=$a; done
+#   make -C multitalent_amd/csrc variant NAME=ts UNIT=conv_x16 EXTRA=-DX16_TS=1
 # Layers: 0 = 30->30 @ 2x48x192x192, 4 = 60->60 @ 2x48x96x96 (tools/bench_fwd16.py).  Output: stdout (copy to profiles/).
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
