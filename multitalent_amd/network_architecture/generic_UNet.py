@@ -62,6 +62,7 @@ class Generic_UNet(SegmentationNetwork):
     BASE_NUM_FEATURES_3D = 30
     MAX_NUMPOOL_3D = 999
     MAX_NUM_FILTERS_3D = 320
+    use_this_for_batch_size_computation_3D = 520000000      # the experiment planners' budget, in units of the estimate below
 
     def __init__(self, input_channels, base_num_features, num_classes, num_pool, num_conv_per_stage=2,
                  feat_map_mul_on_downscale=2, conv_op=nn.Conv3d, norm_op=nn.InstanceNorm3d, norm_op_kwargs=None,
@@ -162,3 +163,26 @@ class Generic_UNet(SegmentationNetwork):
         if self._deep_supervision and self.do_ds:
             return tuple(outs)
         return outs[0]
+
+    @staticmethod
+    def compute_approx_vram_consumption(patch_size, num_pool_per_axis, base_num_features, max_num_features, num_modalities,
+                                        num_classes, pool_op_kernel_sizes, deep_supervision=False, conv_per_stage=2):
+        """The experiment planners' size estimate (reference generic_UNet.py:404-442): the number of feature-map elements a training
+        step keeps, summed over the resolutions.  It is the reference's heuristic for its own cards and is kept so that a
+        fingerprint gives the reference's plan; it says nothing about the memory of this library's engine.  -> np.int64."""
+        npool = len(pool_op_kernel_sizes)
+        map_size = np.array(patch_size)
+        voxels = np.prod(map_size, dtype=np.int64)
+        total = np.int64((conv_per_stage * 2 + 1) * voxels * base_num_features + num_modalities * voxels + num_classes * voxels)
+        num_feat = base_num_features
+        for p in range(npool):
+            for axis in range(len(num_pool_per_axis)):
+                map_size[axis] = int(map_size[axis] / pool_op_kernel_sizes[p][axis])
+            voxels = np.prod(map_size, dtype=np.int64)
+            num_feat = min(num_feat * 2, max_num_features)
+            # encoder and decoder convs plus the transposed conv; the bottleneck has the encoder's convs only
+            num_blocks = (conv_per_stage * 2 + 1) if p < (npool - 1) else conv_per_stage
+            total += num_blocks * voxels * num_feat
+            if deep_supervision and p < (npool - 2):
+                total += voxels * num_classes
+        return total

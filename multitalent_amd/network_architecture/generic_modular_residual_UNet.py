@@ -193,6 +193,7 @@ class FabiansUNet(SegmentationNetwork):
     default_blocks_per_stage_encoder = (1, 2, 3, 4, 4, 4, 4, 4, 4, 4, 4)
     default_blocks_per_stage_decoder = (1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1)
     default_min_batch_size = 2
+    use_this_for_batch_size_computation_3D = 727842816.0
 
     def __init__(self, input_channels, base_num_features, num_blocks_per_stage_encoder, feat_map_mul_on_downscale,
                  pool_op_kernel_sizes, conv_kernel_sizes, props, num_classes, num_blocks_per_stage_decoder,
@@ -228,3 +229,28 @@ class FabiansUNet(SegmentationNetwork):
         ds = bool(self.decoder.deep_supervision)
         outs = self.engine().apply(x, all_heads=ds)
         return list(outs) if ds else outs[0]
+
+    @staticmethod
+    def compute_approx_vram_consumption(patch_size, base_num_features, max_num_features, num_modalities, num_classes,
+                                        pool_op_kernel_sizes, num_conv_per_stage_encoder, num_conv_per_stage_decoder,
+                                        feat_map_mul_on_downscale, batch_size):
+        """The experiment planner's size estimate of this network (reference generic_modular_residual_UNet.py:361-373): the
+        residual encoder's (:121-139) plus the plain decoder's (generic_modular_UNet.py:294-321), each times the batch size.  The
+        shapes are divided in floating point, in the reference's order of operations, because the result decides a plan."""
+        def estimate(first, per_stage, stages):
+            shape = np.array(patch_size)
+            total = first
+            num_feat = base_num_features
+            for p in stages:
+                shape = shape / np.array(pool_op_kernel_sizes[p])
+                num_feat = min(num_feat * feat_map_mul_on_downscale, max_num_features)
+                total += per_stage(p) * np.prod(shape) * num_feat
+            return total * batch_size
+
+        npool = len(pool_op_kernel_sizes) - 1
+        voxels = np.prod(np.array(patch_size))
+        enc = estimate((num_conv_per_stage_encoder[0] * 2 + 1) * voxels * base_num_features + num_modalities * voxels,
+                       lambda p: num_conv_per_stage_encoder[p] * 2 + 1, range(1, npool + 1))       # + 1: the conv in the first skip
+        dec = estimate((num_conv_per_stage_decoder[-1] + 1) * voxels * base_num_features + num_classes * voxels,
+                       lambda p: num_conv_per_stage_decoder[-(p + 1)] + 1, range(1, npool))        # + 1: the transposed conv
+        return enc + dec
