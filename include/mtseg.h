@@ -574,6 +574,40 @@ size_t mt_select_kth_f32_workspace(int nranks);
 int mt_select_kth_f32(const float* x, long n, const long* ranks /* host */, int nranks, float* out, void* ws, size_t ws_bytes,
                       mt_stream_t stream);
 int mt_label_presence(const float* seg, long V, uint32_t* bitmap, int32_t* flag, mt_stream_t stream);
+/* The dataset conversion (dataset_conversion/Task100_MultiTalent.py:229-275, copy_and_convert_segmentation; multitalent_amd/
+ * dataset_conversion/Task100_MultiTalent.py).  Additions to ABI 4.
+ * mt_label_convert: one pass over the label volume in[V] IN THE TYPE THE FILE STORES (dtype: MT_LABEL_*; int64 / uint64 files are cast
+ *   to float64 on the host, as get_fdata does) -> the contiguous uint8 volume out[V].  `in` needs the alignment of its elements only
+ *   and `out` none: the body starts where the input is 16-byte aligned and uses 16-byte loads, the voxels before it and after its
+ *   last whole chunk (fewer than 32) are scalar accesses.  HBM-bound at itemsize bytes read and 1 byte written per voxel; no LDS.
+ *   table: HOST array of MT_LABEL_SLOTS entries, built by the caller from (labels_in, labels_out) in the reference's order (the last
+ *   pair that lists a label wins); table[l] is the output 0..255 of input label l, or MT_LABEL_UNLISTED.  It is passed to the
+ *   kernel by value (no device table, nothing to keep alive).  Per voxel v, compared as the double it widens to:
+ *     not (v > 1e-20)                         out = 0, never an error: zero, negatives, 1e-20 itself and NaN; table[0] never applies;
+ *     an integer l in 1..1022 that is listed   out = table[l];
+ *     anything else                            out = 0 and the voxel is UNEXPECTED: a fraction, +inf, an integer that is not listed
+ *                                              or lies beyond the table.
+ *   report (device uint64[2], 8-byte aligned, written by the call): report[0] = the number of unexpected voxels, report[1] = the
+ *   smallest unexpected value as the bits of its double (an order-preserving key: every such value is positive), or
+ *   0xffffffffffffffff when there is none.  The reference raises at the first offender of its sorted uniques, which is that value;
+ *   whether unexpected voxels are an error (sanity_check) is the caller's decision.  Integer atomics only (a 64-bit add and a 64-bit
+ *   min): bit-identical from run to run.  An unknown dtype, V < 1, a table entry above 255 that is not MT_LABEL_UNLISTED or a
+ *   misaligned pointer is MT_EINVAL before any launch.
+ * mt_label_convert_round: the voxels one full round of the grid-stride loop covers for that dtype on the current device (the launch
+ *   grid is capped there); 0 for an unknown dtype. */
+#define MT_LABEL_U8 0
+#define MT_LABEL_I8 1
+#define MT_LABEL_I16 2
+#define MT_LABEL_U16 3
+#define MT_LABEL_I32 4
+#define MT_LABEL_U32 5
+#define MT_LABEL_F32 6
+#define MT_LABEL_F64 7
+#define MT_LABEL_SLOTS 1023               /* input labels 0..1022, the range of mt_label_presence */
+#define MT_LABEL_UNLISTED 0xffff
+int mt_label_convert(const void* in, int dtype, long V, const uint16_t* table /* host */, uint8_t* out, uint64_t* report,
+                     mt_stream_t stream);
+long mt_label_convert_round(int dtype);
 /* Training batches from cases kept on the device (training/dataloading/device_loading.py).  Additions to ABI 4.
  * mt_patch_gather: the crop and np.pad of DataLoader3D.generate_train_batch (dataset_loading.py:338-372; the box arithmetic of
  *   :259-336 stays on the host) for n <= MT_PATCH_MAX_SRC samples in ONE launch.  srcs: HOST array of n descriptors, passed to the

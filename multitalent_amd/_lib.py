@@ -64,6 +64,8 @@ MT_F32, MT_BF16, MT_F16 = 0, 1, 2
 MT_PATCH_MAX_SRC = 16
 MT_PAD_CONSTANT, MT_PAD_EDGE = 0, 1
 MT_ABI_VERSION = 4
+MT_LABEL_SLOTS, MT_LABEL_UNLISTED = 1023, 0xffff
+MT_LABEL_DTYPES = {'uint8': 0, 'int8': 1, 'int16': 2, 'uint16': 3, 'int32': 4, 'uint32': 5, 'float32': 6, 'float64': 7}
 
 _vp, _i, _l, _f, _d, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_size_t
 _P = C.POINTER
@@ -152,6 +154,8 @@ SIGNATURES = {
     'mt_select_kth_f32_workspace': (_sz, [_i]),
     'mt_select_kth_f32': (_i, [_vp, _l, _vp, _i, _vp, _vp, _sz, _vp]),
     'mt_label_presence': (_i, [_vp, _l, _vp, _vp, _vp]),
+    'mt_label_convert': (_i, [_vp, _i, _l, _P(C.c_uint16), _vp, _vp, _vp]),
+    'mt_label_convert_round': (_l, [_i]),
     'mt_patch_gather': (_i, [_P(mt_patch_src_t), _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     'mt_seg_narrow': (_i, [_vp, _l, _vp, _vp, _vp]),
     'mt_head_flip_accumulate': (_i, [_P(mt_pointwise_t), _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),

@@ -513,15 +513,61 @@ __global__ __launch_bounds__(256) void softmax_loss_fwd_kernel(const float* __re
   }
 }
 
+// More than 16 classes (up to 64: Task100's 47 labels through a softmax trainer): one wave per voxel, lane = class, as the MultiTalent
+// kernels.  The maximum and the sum of the softmax are wave reductions, every lane keeps the three sums of its own class, and the
+// four waves of a block are combined in a fixed order: no register array per class, the same result from run to run.
+__device__ __forceinline__ float mt_wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+__global__ __launch_bounds__(256) void softmax_loss_fwd_wide_kernel(const float* __restrict__ logits, int cs,
+                                                                    const float* __restrict__ target, long V, int C, int nblk,
+                                                                    float* __restrict__ part) {
+  __shared__ float red[4][64 * 3 + 1];
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long v0 = (long)blockIdx.x * LS_VB;
+  const long v1 = (v0 + LS_VB < V) ? v0 + LS_VB : V;
+  const bool act = lane < C;
+  float tp = 0.f, fp = 0.f, fn = 0.f, ce = 0.f;
+  for (long v = v0 + wave; v < v1; v += 4) {
+    const size_t e = (size_t)b * V + v;
+    const int lab = (int)target[e];
+    const float x = act ? logits[e * cs + lane] : -3.0e38f;
+    const float mx = mt_wave_max(x);
+    const float ex = act ? __expf(x - mx) : 0.f;
+    const float p = ex / mt_wave_sum(ex);
+    if (act) {
+      const float y = (lab == lane) ? 1.f : 0.f;
+      tp += p * y; fp += p * (1.f - y); fn += (1.f - p) * y;
+      if (lab == lane) ce -= __logf(fmaxf(p, 1e-38f));
+    }
+  }
+  ce = mt_wave_sum(ce);
+  red[wave][lane * 3] = tp; red[wave][lane * 3 + 1] = fp; red[wave][lane * 3 + 2] = fn;
+  if (lane == 0) red[wave][64 * 3] = ce;
+  __syncthreads();
+  if (threadIdx.x < C * 4) {
+    const int c = threadIdx.x >> 2, k = threadIdx.x & 3;
+    float s = 0.f;
+    if (k == 0) { if (c == 0) s = red[0][64 * 3] + red[1][64 * 3] + red[2][64 * 3] + red[3][64 * 3]; }
+    else s = red[0][c * 3 + k - 1] + red[1][c * 3 + k - 1] + red[2][c * 3 + k - 1] + red[3][c * 3 + k - 1];
+    part[(((size_t)b * nblk + blockIdx.x) * C + c) * 4 + k] = s;
+  }
+}
+
 extern "C" int mt_softmax_dice_ce_fwd(const float* logits, int cs, const float* target, int B, long V, int C,
                                       float* stats, void* ws, size_t ws_bytes, mt_stream_t stream) {
-  MT_REQUIRE(logits && target && stats && B > 0 && V > 0 && C > 1 && C <= 16, "softmax_dice_ce_fwd: bad args (2 <= C <= 16)");
+  MT_REQUIRE(logits && target && stats && B > 0 && V > 0 && C > 1 && C <= 64, "softmax_dice_ce_fwd: bad args (2 <= C <= 64)");
   if (ws == nullptr || ws_bytes < mt_loss_workspace(B, V, C)) { mt_set_error("softmax_dice_ce_fwd: workspace too small"); return MT_EWORKSPACE; }
   const int nblk = mt_cdiv(V, LS_VB);
   hipStream_t st = (hipStream_t)stream;
   if (C <= 4) hipLaunchKernelGGL(softmax_loss_fwd_kernel<4>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
   else if (C <= 8) hipLaunchKernelGGL(softmax_loss_fwd_kernel<8>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
-  else hipLaunchKernelGGL(softmax_loss_fwd_kernel<16>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
+  else if (C <= 16) hipLaunchKernelGGL(softmax_loss_fwd_kernel<16>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
+  else hipLaunchKernelGGL(softmax_loss_fwd_wide_kernel, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
   hipLaunchKernelGGL(loss_stats_finalize_kernel, dim3(C * 4, B), dim3(64), 0, st, (const float*)ws, nblk, C, stats);
   MT_CHECK_LAUNCH("softmax_dice_ce_fwd");
   return MT_OK;
@@ -571,14 +617,42 @@ __global__ __launch_bounds__(256) void softmax_loss_bwd_kernel(const float* __re
   }
 }
 
+// 16 < C <= 64: one wave per voxel, lane = class (see softmax_loss_fwd_wide_kernel).
+__global__ __launch_bounds__(256) void softmax_loss_bwd_wide_kernel(const float* __restrict__ logits, int cs,
+                                                                    const float* __restrict__ target, long V, int C,
+                                                                    const float* __restrict__ gstats, float* __restrict__ dlogits, int dcs) {
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool act = lane < C;
+  const float ce_coef = gstats[(size_t)b * C * 4];
+  const float a_tp = act ? gstats[((size_t)b * C + lane) * 4 + 1] : 0.f;
+  const float a_fp = act ? gstats[((size_t)b * C + lane) * 4 + 2] : 0.f;
+  const float a_fn = act ? gstats[((size_t)b * C + lane) * 4 + 3] : 0.f;
+  const long v0 = (long)blockIdx.x * LS_VB;
+  const long v1 = (v0 + LS_VB < V) ? v0 + LS_VB : V;
+  for (long v = v0 + wave; v < v1; v += 4) {
+    const size_t e = (size_t)b * V + v;
+    const int lab = (int)target[e];
+    const float x = act ? logits[e * cs + lane] : -3.0e38f;
+    const float mx = mt_wave_max(x);
+    const float ex = act ? __expf(x - mx) : 0.f;
+    const float p = ex / mt_wave_sum(ex);
+    const float y = (lab == lane) ? 1.f : 0.f;
+    const float G = y * (a_tp - a_fn) + (1.f - y) * a_fp;
+    const float dot = mt_wave_sum(p * G);
+    if (act) dlogits[e * dcs + lane] = ce_coef * (p - y) + p * (G - dot);
+  }
+}
+
 extern "C" int mt_softmax_dice_ce_bwd(const float* logits, int cs, const float* target, int B, long V, int C,
                                       const float* gstats, float* dlogits, int dcs, mt_stream_t stream) {
-  MT_REQUIRE(logits && target && gstats && dlogits && B > 0 && V > 0 && C > 1 && C <= 16, "softmax_dice_ce_bwd: bad args");
+  MT_REQUIRE(logits && target && gstats && dlogits && B > 0 && V > 0 && C > 1 && C <= 64, "softmax_dice_ce_bwd: bad args (2 <= C <= 64)");
   const int nblk = mt_cdiv(V, LS_VB);
   hipStream_t st = (hipStream_t)stream;
   if (C <= 4) hipLaunchKernelGGL(softmax_loss_bwd_kernel<4>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
   else if (C <= 8) hipLaunchKernelGGL(softmax_loss_bwd_kernel<8>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
-  else hipLaunchKernelGGL(softmax_loss_bwd_kernel<16>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
+  else if (C <= 16) hipLaunchKernelGGL(softmax_loss_bwd_kernel<16>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
+  else hipLaunchKernelGGL(softmax_loss_bwd_wide_kernel, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
   MT_CHECK_LAUNCH("softmax_dice_ce_bwd");
   return MT_OK;
 }

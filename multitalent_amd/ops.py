@@ -1145,6 +1145,46 @@ def label_presence(seg, what='label map'):
     return [int(b) - 1 for b in np.flatnonzero(bits)]
 
 
+_CONV = "the label conversion of the dataset conversion runs"
+LABEL_CONVERT_DTYPES = _lib.MT_LABEL_DTYPES
+
+
+def label_convert_round(dtype):
+    """The voxels one full round of mt_label_convert's grid-stride loop covers for a numpy dtype name on the current device."""
+    return int(_lib.load().mt_label_convert_round(LABEL_CONVERT_DTYPES[np.dtype(dtype).name]))
+
+
+def label_convert(seg, table, out=None):
+    """seg: contiguous device tensor of a label volume in the type its file stores (uint8, int8, int16, uint16, int32, uint32,
+    float32 or float64; any element-aligned view).  table: uint16 numpy array of MT_LABEL_SLOTS entries, the output 0..255 of every
+    input label 0..1022 or MT_LABEL_UNLISTED (dataset_conversion.Task100_MultiTalent.label_table builds it).
+    -> (uint8 device tensor of seg's shape, number of unexpected voxels, the smallest unexpected value as a float or None): a
+    voxel above 1e-20 that is no listed label is unexpected and becomes 0 (one read-back of two words).  `out`: a contiguous uint8
+    device tensor of as many elements to write into, of any alignment.  See mt_label_convert."""
+    _require_device(_CONV, seg)
+    name = str(seg.dtype).replace('torch.', '')
+    if name not in LABEL_CONVERT_DTYPES:
+        raise ValueError("label_convert: a %s volume is not converted on the device (cast int64 / uint64 to float64 first)" % name)
+    table = np.ascontiguousarray(table)
+    if table.dtype != np.uint16 or table.shape != (_lib.MT_LABEL_SLOTS,):
+        raise ValueError("label_convert: the table must be uint16 [%d]" % _lib.MT_LABEL_SLOTS)
+    V = int(seg.numel())
+    if V < 1:
+        raise ValueError("label_convert: the volume is empty")
+    assert seg.is_contiguous()
+    if out is None:
+        out = torch.empty(seg.shape, dtype=torch.uint8, device=seg.device)
+    _require_device(_CONV, out)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == V and out.device == seg.device
+    report = torch.empty(2, dtype=torch.int64, device=seg.device)
+    with torch.cuda.device(seg.device):
+        _lib.check(_lib.load().mt_label_convert(_ptr(seg), LABEL_CONVERT_DTYPES[name], V, table.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                _ptr(out), _ptr(report), _stream()), 'label_convert')
+    host = report.cpu().numpy()
+    count = int(host[0])
+    return out, count, (float(host[1:2].view(np.float64)[0]) if count else None)
+
+
 _LOAD = "the patch gather of the device loader runs"
 PAD_MODES = {'constant': _lib.MT_PAD_CONSTANT, 'edge': _lib.MT_PAD_EDGE}
 
