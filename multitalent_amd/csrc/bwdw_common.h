@@ -1,4 +1,4 @@
-// Parameter blocks and host helpers shared by the convolution translation units: conv_lds.hip (forward, backward-data, weight packing),
+// Parameter blocks and host helpers shared by the convolution translation units: conv_lds.hip (forward, backward-data: one dispatch decision each, conv_resolve / bwdd_resolve; weight packing),
 // conv_bwdw.hip (backward-weight: plans, the one dispatch decision, the reduce), and the single-family units bwdw_tr16.hip and conv_x16.hip,
 // whose launchers are declared here and whose dispatch stays with the caller.
 #pragma once

@@ -1909,82 +1909,6 @@ static int pick_cfg(const mt_conv3d_t* p) {
   return best;
 }
 
-// which kernel family serves a problem, and with which tile shape
-enum ConvKind { CONV_FAST = 0, CONV_RT = 1, CONV_GENERIC = 2, CONV_FAST_STRIDED = 3, CONV_TAPSPLIT = 4, CONV_STEM = 5, CONV_WINO = 6, CONV_BF16 = 7 };
-struct ConvPlan { int kind; int cfg; };
-static bool conv_is_fast(const mt_conv3d_t* p);
-static bool conv_rt_ok(const mt_conv3d_t* p);
-static int pick_rt_cfg(const mt_conv3d_t* p);
-static bool conv_fast_strided_ok(const mt_conv3d_t* p);
-static bool conv_wino_ok(const mt_conv3d_t* p);
-static bool conv_gather_ok(const mt_conv3d_t* p);
-static bool gather_use_bf16(const mt_conv3d_t* p);
-static int launch_gather(const mt_conv3d_t* p, hipStream_t st);
-static bool conv_is_133(const mt_conv3d_t* p);
-static int conv_bf16_cfg(const mt_conv3d_t* p);
-static bool strided_use_bf16(const mt_conv3d_t* p);
-static int conv_matrix_type(const mt_conv3d_t* p);
-// mt_conv3d_t.select field as the legacy three-way switch: 0 = never this family, 1 = the library's policy, 2 = wherever eligible
-static ConvPlan conv_plan(const mt_conv3d_t* p) {
-  ConvPlan pl; pl.kind = CONV_GENERIC; pl.cfg = pick_cfg(p);
-  if (p->mma == 1) {                      // bf16 matrix inputs where the bf16 kernel serves the problem; fp32 kernels elsewhere
-    const int bc = conv_bf16_cfg(p);
-    if (bc >= 0) { pl.kind = CONV_BF16; pl.cfg = bc; return pl; }
-  }
-  if (conv_is_fast(p) && p->osD <= 0 && p->nsrc == 1 && p->Cin == 1 && p->csplit >= p->Cout &&
-      (double)p->Do * p->Ho * p->Wo * p->ocs0 * 4.0 < 2147483648.0) { pl.kind = CONV_STEM; pl.cfg = 0; return pl; }
-  if (conv_is_fast(p) && pl.cfg >= 0 && pl.cfg <= 2 && p->osD <= 0 && conv_wino_ok(p)) { pl.kind = CONV_WINO; return pl; }
-  if (conv_is_fast(p) && pl.cfg >= 0 && pl.cfg <= 2 && p->osD <= 0) {
-    pl.kind = CONV_FAST;
-    // low-resolution stages: fewer than two workgroups per CU -> split the taps over the waves instead
-    const int use_ts = mt_sel3(p, MT_SEL_TAPSPLIT);
-    int TD, TH, TW; cfg_tile(kCfgs[pl.cfg], &TD, &TH, &TW);
-    const long wgs = (long)p->N * mt_cdiv(p->Do, TD) * mt_cdiv(p->Ho, TH) * mt_cdiv(p->Wo, TW) * mt_cdiv(p->Cout, 32);
-    if (use_ts && wgs < 300 && p->csplit >= p->Cout && (double)p->Do * p->Ho * p->Wo * p->ocs0 * 4.0 < 2147483648.0) pl.kind = CONV_TAPSPLIT;
-    return pl;
-  }
-  if (conv_is_133(p) && pl.cfg >= 0 && pl.cfg <= 2 && p->osD <= 0 && p->Cin >= 8) { pl.kind = CONV_FAST; return pl; }      // compile-time taps instead of conv_rt
-  if (conv_fast_strided_ok(p)) {
-    pl.kind = CONV_FAST_STRIDED; pl.cfg = 0;
-    // fewer workgroups than CUs in the 2x4x8 x 64-channel tiling: one 32-voxel tile x 32 channels per workgroup, taps over the waves
-    const int g_tapsplit = mt_sel3(p, MT_SEL_TAPSPLIT);
-    const long wgs = (long)p->N * mt_cdiv(p->Do, 2) * mt_cdiv(p->Ho, 4) * mt_cdiv(p->Wo, 8) * mt_cdiv(p->Cout, 64);
-    const int sd = conv_src_dtype(p);
-    const bool inst = strided_use_bf16(p) ? mt_is16(sd) && (p->odtype == sd || p->odtype == MT_F32) : (sd == MT_F32 && p->odtype == MT_F32 && conv_fast_vec(p) == 2);
-    if (g_tapsplit && (wgs < 256 || g_tapsplit >= 2) && inst) pl.kind = CONV_TAPSPLIT;
-    return pl;
-  }
-  if (conv_rt_ok(p)) {
-    const int i = pick_rt_cfg(p);
-    if (i >= 0) { pl.kind = CONV_RT; pl.cfg = i; return pl; }
-  }
-  return pl;
-}
-extern "C" int mt_conv3d_ck(const mt_conv3d_t* p) {
-  const ConvPlan pl = conv_plan(p);
-  if (pl.kind == CONV_WINO) return WCK;
-  if (pl.kind == CONV_BF16) return FCK;
-  if (pl.kind == CONV_RT && conv_gather_ok(p)) return FCK;          // (conv_gather_kernel chunks the channels by FCK)
-  return pl.cfg < 0 ? -1 : kCfgs[pl.cfg].CK;
-}
-extern "C" int mt_conv3d_pack_layout(const mt_conv3d_t* p) {      // layout argument of mt_pack_conv_weights for this problem
-  const int k = conv_plan(p).kind;
-  if (k == CONV_RT && conv_gather_ok(p) && gather_use_bf16(p)) return 3;
-  const int l16 = conv_matrix_type(p) == MT_F16 ? 4 : 3;
-  if ((k == CONV_FAST_STRIDED || k == CONV_TAPSPLIT) && strided_use_bf16(p)) return l16;
-  return k == CONV_WINO ? 2 : k == CONV_BF16 ? l16 : 1;
-}
-extern "C" int mt_conv3d_stats_blocks(const mt_conv3d_t* p) {
-  const ConvPlan pl = conv_plan(p);
-  if (pl.cfg < 0) return -1;
-  if (pl.kind == CONV_FAST_STRIDED) return mt_cdiv(p->Do, 2) * mt_cdiv(p->Ho, 4) * mt_cdiv(p->Wo, 8);
-  if (pl.kind == CONV_TAPSPLIT) return mt_cdiv(p->Do, 2) * mt_cdiv(p->Ho, 4) * mt_cdiv(p->Wo, 4);
-  if (pl.kind == CONV_WINO) return mt_cdiv(p->Do, 4) * mt_cdiv(p->Ho, 4) * mt_cdiv(p->Wo, 16);
-  if (pl.kind == CONV_BF16) { int TD, TH, TW; cfg_tile(kBfCfgs[pl.cfg], &TD, &TH, &TW); return mt_cdiv(p->Do, TD) * mt_cdiv(p->Ho, TH) * mt_cdiv(p->Wo, TW); }
-  int TD, TH, TW; cfg_tile(kCfgs[pl.cfg], &TD, &TH, &TW);
-  return mt_cdiv(p->Do, TD) * mt_cdiv(p->Ho, TH) * mt_cdiv(p->Wo, TW);
-}
-
 static int conv_validate(const mt_conv3d_t* p) {
   MT_REQUIRE(p != nullptr, "conv3d: null params");
   MT_REQUIRE(p->nsrc == 1 || p->nsrc == 2, "conv3d: nsrc must be 1 or 2 (got %d)", p->nsrc);
@@ -1999,6 +1923,7 @@ static int conv_validate(const mt_conv3d_t* p) {
   return MT_OK;
 }
 
+// ---- eligibility of the kernel families (read by conv_resolve alone)
 static bool conv_slopes_ok(const mt_conv3d_t* p) {     // the lean staging computes LeakyReLU as max(t, slope*t)
   for (int i = 0; i < p->nsrc; ++i)
     if (p->src[i].scale != nullptr && !(p->src[i].slope >= 0.f && p->src[i].slope <= 1.f)) return false;
@@ -2012,41 +1937,21 @@ static bool conv_is_fast(const mt_conv3d_t* p) {
     if ((double)p->Di * p->Hi * p->Wi * p->src[i].cs * 4.0 >= 2147483648.0) return false;  // 31-bit buffer offsets per sample
   return true;
 }
-
-// matrix type of a problem served by the 16-bit matrix kernels (p->mma == 1): fp16 sources multiply as fp16 (forward over fp16
-// activations), everything else as bf16.  The packed weights must match: layout 4 (fp16) / 3 (bf16).
-static int conv_matrix_type(const mt_conv3d_t* p) { return conv_src_dtype(p) == MT_F16 ? MT_F16 : MT_BF16; }
+// 1x3x3, stride 1, pad (0,1,1): the first stage of the residual encoder (generic_modular_residual_UNet.py:28-118, plan kernels)
+static bool conv_is_133(const mt_conv3d_t* p) {
+  if (!conv_slopes_ok(p)) return false;
+  if (!(p->KD == 1 && p->KH == 3 && p->KW == 3 && p->SD == 1 && p->SH == 1 && p->SW == 1 && p->PD == 0 && p->PH == 1 &&
+        p->PW == 1 && p->dilD == 1 && p->dilH == 1 && p->dilW == 1)) return false;
+  for (int i = 0; i < p->nsrc; ++i)
+    if ((double)p->Di * p->Hi * p->Wi * p->src[i].cs * 4.0 >= 2147483648.0) return false;
+  return true;
+}
 // whether the destination(s) can be written as bf16 dwords (channel pairs: even channel counts / strides / split, dword-aligned bases)
-static bool conv_out_pairs_ok(const mt_conv3d_t* p) {
+static bool out_pairs_aligned(const mt_conv3d_t* p) {
   if ((p->Cout & 1) || (p->ocs0 & 1) || (((uintptr_t)p->out0) & 3)) return false;
   if (p->csplit < p->Cout && ((p->csplit & 1) || (p->ocs1 & 1) || (((uintptr_t)p->out1) & 3))) return false;
   return true;
 }
-
-template <int MW, int RH, int TD, int VEC, int KD = 3>
-static int launch_fast2(const mt_conv3d_t* p, const ConvCfg& g, hipStream_t st) {
-  ConvKParams P;
-  P.c = *p;
-  if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
-  int TDv, TH, TW; TDv = g.TD; TH = (32 / g.MW) * g.RH; TW = g.MW;
-  P.tilesD = mt_cdiv(p->Do, TDv); P.tilesH = mt_cdiv(p->Ho, TH); P.tilesW = mt_cdiv(p->Wo, TW);
-  P.nsb = P.tilesD * P.tilesH * P.tilesW;
-  P.ntaps = KD * 9; P.dbg = 0; P.stagger = 0;
-  P.nchunks = mt_build_chunks(p->src[0].C, p->nsrc == 2 ? p->src[1].C : 0, FCK, P.chunk);
-  MT_REQUIRE(P.nchunks > 0, "conv3d: too many channel chunks (Cin=%d)", p->Cin);
-  constexpr int TH_ = (32 / MW) * RH;
-  const size_t ldsb = stage_lds_bytes<TD + KD - 1, TH_ + 2, MW + 2, VEC>();
-  dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(p->Cout, 32), 1);
-  auto kfn = conv_fast_kernel<MW, RH, TD, VEC, KD>;
-  if (ldsb > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    if (e != hipSuccess) { mt_set_error("conv3d: cannot raise dynamic LDS to %zu: %s", ldsb, hipGetErrorString(e)); return MT_EHIP; }
-  }
-  hipLaunchKernelGGL(kfn, grid, dim3(256), ldsb, st, P);
-  MT_CHECK_LAUNCH("conv3d_fast");
-  return MT_OK;
-}
-
 static bool conv_fast_strided_ok(const mt_conv3d_t* p) {
   if (!conv_slopes_ok(p)) return false;
   if (!(p->KD == 3 && p->KH == 3 && p->KW == 3 && p->PD == 1 && p->PH == 1 && p->PW == 1)) return false;
@@ -2055,126 +1960,6 @@ static bool conv_fast_strided_ok(const mt_conv3d_t* p) {
   for (int i = 0; i < p->nsrc; ++i)
     if ((double)p->Di * p->Hi * p->Wi * p->src[i].cs * 4.0 >= 2147483648.0) return false;
   if ((double)p->Do * p->Ho * p->Wo * p->ocs0 * 4.0 >= 2147483648.0) return false;
-  return true;
-}
-template <int SD>
-static int launch_fast_strided_t(const mt_conv3d_t* p, hipStream_t st) {
-  constexpr int TD = 2, TH = 4, TW = 8, LD = (TD - 1) * SD + 3, LH = (TH - 1) * 2 + 3, LW = (TW - 1) * 2 + 3;
-  ConvKParams P;
-  P.c = *p;
-  if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
-  P.tilesD = mt_cdiv(p->Do, TD); P.tilesH = mt_cdiv(p->Ho, TH); P.tilesW = mt_cdiv(p->Wo, TW);
-  P.nsb = P.tilesD * P.tilesH * P.tilesW;
-  P.ntaps = 27; P.dbg = 0; P.stagger = 0;
-  P.nchunks = mt_build_chunks(p->src[0].C, p->nsrc == 2 ? p->src[1].C : 0, FCK, P.chunk);
-  MT_REQUIRE(P.nchunks > 0, "conv3d: too many channel chunks (Cin=%d)", p->Cin);
-  dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(p->Cout, 64), 1);
-  if (strided_use_bf16(p)) {
-    const int sd = conv_src_dtype(p);
-    // 16-bit source: fp16 activations multiply as fp16 (the forward pass), bf16 sources as bf16; the destination has the source's
-    // type, or fp32 (a level the engine keeps in fp32)
-#define MT_FS_LAUNCH(XS_, OS_, MTY_, VEC_) hipLaunchKernelGGL((conv_fast_strided_kernel<SD, 2, 2, VEC_, true, XS_, OS_, MTY_>), grid, dim3(256), (bstage_lds_bytes<LD, LH, LW, VEC_, 4>()), st, P)
-    if (sd == MT_F16 && p->odtype == MT_F16) MT_FS_LAUNCH(MT_F16, MT_F16, MT_F16, 4);
-    else if (sd == MT_F16) MT_FS_LAUNCH(MT_F16, MT_F32, MT_F16, 4);
-    else if (sd == MT_BF16 && p->odtype == MT_BF16) MT_FS_LAUNCH(MT_BF16, MT_BF16, MT_BF16, 4);
-    else if (sd == MT_BF16) MT_FS_LAUNCH(MT_BF16, MT_F32, MT_BF16, 4);
-    else MT_FS_LAUNCH(MT_F32, MT_F32, MT_BF16, 2);
-#undef MT_FS_LAUNCH
-  } else if (conv_fast_vec(p) == 2) {
-    hipLaunchKernelGGL((conv_fast_strided_kernel<SD, 2, 2, 2>), grid, dim3(256), (stage_lds_bytes<LD, LH, LW, 2>()), st, P);
-  } else {
-    constexpr size_t l1 = stage_lds_bytes<LD, LH, LW, 1>();
-    auto kfn = conv_fast_strided_kernel<SD, 2, 2, 1>;
-    if (l1 > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1);
-      if (e != hipSuccess) { mt_set_error("conv3d: cannot raise dynamic LDS: %s", hipGetErrorString(e)); return MT_EHIP; }
-    }
-    hipLaunchKernelGGL(kfn, grid, dim3(256), l1, st, P);
-  }
-  MT_CHECK_LAUNCH("conv3d_fast_strided");
-  return MT_OK;
-}
-static int launch_fast_strided(const mt_conv3d_t* p, hipStream_t st) {
-  return p->SD == 2 ? launch_fast_strided_t<2>(p, st) : launch_fast_strided_t<1>(p, st);
-}
-
-static int launch_tapsplit(const mt_conv3d_t* p, hipStream_t st) {
-  ConvKParams P;
-  P.c = *p;
-  if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
-  P.tilesD = mt_cdiv(p->Do, 2); P.tilesH = mt_cdiv(p->Ho, 4); P.tilesW = mt_cdiv(p->Wo, 4);
-  P.nsb = P.tilesD * P.tilesH * P.tilesW;
-  P.ntaps = 27; P.dbg = 0; P.stagger = 0;
-  P.nchunks = mt_build_chunks(p->src[0].C, p->nsrc == 2 ? p->src[1].C : 0, FCK, P.chunk);
-  MT_REQUIRE(P.nchunks > 0, "conv3d: too many channel chunks (Cin=%d)", p->Cin);
-  dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(p->Cout, 32), 1);
-  const size_t red = (size_t)4 * 16 * 64 * sizeof(float);
-  if (p->SH == 2) {                        // strided stage convs (conv_plan: fp32 with 8-byte channel pairs, or 16-bit storage)
-    const int sd = conv_src_dtype(p);
-#define MT_TS_STRIDED(SD_)                                                                                                           \
-    do {                                                                                                                             \
-      constexpr int LD_ = SD_ + 3, LH_ = 9, LW_ = 9;                                                                                 \
-      if (strided_use_bf16(p)) {                                                                                                     \
-        size_t l = bstage_lds_bytes<LD_, LH_, LW_, 4, 4>(); if (l < red) l = red;                                                    \
-        if (sd == MT_F16 && p->odtype == MT_F16) hipLaunchKernelGGL((conv_tapsplit_kernel<4, true, MT_F16, MT_F16, MT_F16, SD_, 2, 2>), grid, dim3(256), l, st, P);       \
-        else if (sd == MT_F16) hipLaunchKernelGGL((conv_tapsplit_kernel<4, true, MT_F16, MT_F32, MT_F16, SD_, 2, 2>), grid, dim3(256), l, st, P);                        \
-        else if (p->odtype == MT_BF16) hipLaunchKernelGGL((conv_tapsplit_kernel<4, true, MT_BF16, MT_BF16, MT_BF16, SD_, 2, 2>), grid, dim3(256), l, st, P);             \
-        else hipLaunchKernelGGL((conv_tapsplit_kernel<4, true, MT_BF16, MT_F32, MT_BF16, SD_, 2, 2>), grid, dim3(256), l, st, P);                                        \
-      } else {                                                                                                                       \
-        size_t l = stage_lds_bytes<LD_, LH_, LW_, 2>(); if (l < red) l = red;                                                        \
-        hipLaunchKernelGGL((conv_tapsplit_kernel<2, false, MT_F32, MT_F32, MT_BF16, SD_, 2, 2>), grid, dim3(256), l, st, P);         \
-      }                                                                                                                              \
-    } while (0)
-    if (p->SD == 2) MT_TS_STRIDED(2); else MT_TS_STRIDED(1);
-#undef MT_TS_STRIDED
-  } else if (strided_use_bf16(p)) {        // same eligibility: mma == 1, >= 16 even channels, aligned sources
-    const int sd = conv_src_dtype(p);
-    if (sd == MT_F32) {
-      size_t l = bstage_lds_bytes<4, 6, 6, 2, 4>(); if (l < red) l = red;
-      hipLaunchKernelGGL((conv_tapsplit_kernel<2, true>), grid, dim3(256), l, st, P);
-    } else {
-      size_t l = bstage_lds_bytes<4, 6, 6, 4, 4>(); if (l < red) l = red;
-      if (sd == MT_F16 && p->odtype == MT_F16) hipLaunchKernelGGL((conv_tapsplit_kernel<4, true, MT_F16, MT_F16, MT_F16>), grid, dim3(256), l, st, P);
-      else if (sd == MT_F16) hipLaunchKernelGGL((conv_tapsplit_kernel<4, true, MT_F16, MT_F32, MT_F16>), grid, dim3(256), l, st, P);
-      else if (p->odtype == MT_BF16) hipLaunchKernelGGL((conv_tapsplit_kernel<4, true, MT_BF16, MT_BF16, MT_BF16>), grid, dim3(256), l, st, P);
-      else hipLaunchKernelGGL((conv_tapsplit_kernel<4, true, MT_BF16, MT_F32, MT_BF16>), grid, dim3(256), l, st, P);
-    }
-  } else if (conv_fast_vec(p) == 2) {
-    size_t l = stage_lds_bytes<4, 6, 6, 2>(); if (l < red) l = red;
-    hipLaunchKernelGGL((conv_tapsplit_kernel<2>), grid, dim3(256), l, st, P);
-  } else {
-    size_t l = stage_lds_bytes<4, 6, 6, 1>(); if (l < red) l = red;
-    hipLaunchKernelGGL((conv_tapsplit_kernel<1>), grid, dim3(256), l, st, P);
-  }
-  MT_CHECK_LAUNCH("conv3d_tapsplit");
-  return MT_OK;
-}
-
-static int launch_stem(const mt_conv3d_t* p, hipStream_t st) {
-  ConvKParams P;
-  P.c = *p;
-  P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0;
-  P.tilesD = mt_cdiv(p->Do, 2); P.tilesH = mt_cdiv(p->Ho, 4); P.tilesW = mt_cdiv(p->Wo, 32);
-  P.nsb = P.tilesD * P.tilesH * P.tilesW;
-  P.ntaps = 27; P.dbg = 0; P.stagger = 0;
-  P.nchunks = mt_build_chunks(1, 0, FCK, P.chunk);
-  dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(p->Cout, 32), 1);
-  if (p->odtype == MT_F16) hipLaunchKernelGGL((conv_stem_kernel<MT_F16>), grid, dim3(256), 0, st, P);
-  else if (p->odtype == MT_BF16) hipLaunchKernelGGL((conv_stem_kernel<MT_BF16>), grid, dim3(256), 0, st, P);
-  else hipLaunchKernelGGL((conv_stem_kernel<MT_F32>), grid, dim3(256), 0, st, P);
-  MT_CHECK_LAUNCH("conv3d_stem");
-  return MT_OK;
-}
-
-// Winograd eligibility: FAST geometry, 8-byte channel pairs in every source, one destination, enough workgroups to fill
-// the chip with 4x4x16 tiles and enough input channels to amortise the transforms
-// 1x3x3, stride 1, pad (0,1,1): the first stage of the residual encoder (generic_modular_residual_UNet.py:28-118, plan kernels)
-static bool conv_is_133(const mt_conv3d_t* p) {
-  if (!conv_slopes_ok(p)) return false;
-  if (!(p->KD == 1 && p->KH == 3 && p->KW == 3 && p->SD == 1 && p->SH == 1 && p->SW == 1 && p->PD == 0 && p->PH == 1 &&
-        p->PW == 1 && p->dilD == 1 && p->dilH == 1 && p->dilW == 1)) return false;
-  for (int i = 0; i < p->nsrc; ++i)
-    if ((double)p->Di * p->Hi * p->Wi * p->src[i].cs * 4.0 >= 2147483648.0) return false;
   return true;
 }
 // ---- bf16 matrix inputs (conv_bf16.inc)
@@ -2198,73 +1983,19 @@ static int conv_bf16_cfg(const mt_conv3d_t* p) {
   if (wgs < 256 && use != 2) return -1;          // low-resolution stages stay on the fp32 latency-oriented kernels
   return best;
 }
-static bool strided_use_bf16(const mt_conv3d_t* p) {      // forward strided stage convs in mixed precision
-  const int g_bf16_mode = mt_sel3(p, MT_SEL_M16);
-  constexpr int use = 1;
-  return use && g_bf16_mode && p->mma == 1 && p->Cin >= 16 && conv_fast_vec(p) == 2;
-}
-static int conv_bf16_vec(const mt_conv3d_t*) { return 2; }    // 16-byte staging loads measured slower (0.409 vs 0.372 ms on 32->32)
-template <int MW, int RH, int TD, int VEC, int NT, int NW, int KD = 3, int XS = MT_F32, int OS = MT_F32, int MTY = MT_BF16>
-static int launch_bf16_t(const mt_conv3d_t* p, hipStream_t st) {
-  ConvKParams P;
-  P.c = *p;
-  if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
-  constexpr int TH = (32 / MW) * RH, TW = MW;
-  P.tilesD = mt_cdiv(p->Do, TD); P.tilesH = mt_cdiv(p->Ho, TH); P.tilesW = mt_cdiv(p->Wo, TW);
-  P.nsb = P.tilesD * P.tilesH * P.tilesW;
-  P.ntaps = KD * 9; P.dbg = 0; P.stagger = 0;
-  P.nchunks = mt_build_chunks(p->src[0].C, p->nsrc == 2 ? p->src[1].C : 0, FCK, P.chunk);
-  MT_REQUIRE(P.nchunks > 0, "conv3d: too many channel chunks (Cin=%d)", p->Cin);
-  const size_t ldsb = bstage_lds_bytes<TD + KD - 1, TH + 2, TW + 2, VEC, NW, (BF_SWZ ? BFP_SWZ : BFP)>();
-  dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(mt_cdiv(p->Cout, 32), NT), 1);
-  auto kfn = conv_bf16_kernel<MW, RH, TD, VEC, NT, NW, KD, XS, OS, MTY>;
-  if (ldsb > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    if (e != hipSuccess) { mt_set_error("conv3d: cannot raise dynamic LDS to %zu: %s", ldsb, hipGetErrorString(e)); return MT_EHIP; }
-  }
-  hipLaunchKernelGGL(kfn, grid, dim3(64 * NW), ldsb, st, P);
-  MT_CHECK_LAUNCH("conv3d_bf16");
-  return MT_OK;
-}
-static int launch_bf16(const mt_conv3d_t* p, int cfg, hipStream_t st) {
-  // NT = 2 (64 output channels per workgroup) measured slower: 0.197 vs 0.179 ms on 64->64 @ 24x96x96; 8 waves: no gain
-  // storage: all fp32 (bf16 matrix type), all bf16 (backward-data over gradients) or all fp16 (forward over activations: fp16 matrix
-  // type); 16-bit sources are read as 8-byte groups of four channels, 16-bit destinations written as channel-pair dwords
-  const int sd = conv_src_dtype(p);
-  MT_REQUIRE(sd >= 0 && sd == p->odtype, "conv3d: conv_bf16_kernel takes ONE storage type on all operands (ask mt_conv3d_io_supported)");
-#define MT_BF_CASE(I_, MW_, RH_, TD_, NW_)                                                   \
-  if (cfg == I_) {                                                                           \
-    if (sd == MT_F16) return p->KD == 1 ? launch_bf16_t<MW_, RH_, TD_, 4, 1, NW_, 1, MT_F16, MT_F16, MT_F16>(p, st) : launch_bf16_t<MW_, RH_, TD_, 4, 1, NW_, 3, MT_F16, MT_F16, MT_F16>(p, st); \
-    if (sd == MT_BF16) return p->KD == 1 ? launch_bf16_t<MW_, RH_, TD_, 4, 1, NW_, 1, MT_BF16, MT_BF16, MT_BF16>(p, st) : launch_bf16_t<MW_, RH_, TD_, 4, 1, NW_, 3, MT_BF16, MT_BF16, MT_BF16>(p, st); \
-    return p->KD == 1 ? launch_bf16_t<MW_, RH_, TD_, 2, 1, NW_, 1>(p, st) : launch_bf16_t<MW_, RH_, TD_, 2, 1, NW_>(p, st); \
-  }
-  MT_BF_CASE(0, 32, 4, 4, 4)
-  MT_BF_CASE(1, 32, 4, 2, 4)
-  MT_BF_CASE(2, 16, 4, 2, 4)
-#undef MT_BF_CASE
-  mt_set_error("conv3d bf16: bad tile configuration %d", cfg);
-  return MT_EINVAL;
+static bool strided_use_bf16(const mt_conv3d_t* p) {      // forward strided stage convs (and the tap-split kernel) in mixed precision
+  return mt_sel3(p, MT_SEL_M16) && p->mma == 1 && p->Cin >= 16 && conv_fast_vec(p) == 2;
 }
 
-// conv_x16_kernel (conv_x16.hip): the CONV_BF16 problems on the 4 x 4 x 32 tile with ONE 16-bit storage type on all operands and one
+// conv_x16_kernel (conv_x16.hip): the conv_bf16_kernel problems on the 4 x 4 x 32 tile with ONE 16-bit storage type on all operands and one
 // destination — persistent workgroups, weight fragments in LDS, register prefetch of the next (tile, chunk) step, 16-byte stores.
 // mt_conv3d_t.select MT_SEL_X16: default = where it measured faster than conv_bf16_kernel (one cout tile, or >= 8 channel chunks:
 // tools/bench_fwd16.py) | OFF = conv_bf16_kernel everywhere | FORCE: wherever eligible; max_workgroups caps the persistent grid
 // (tests: several tiles per workgroup)
-static bool conv_x16_geometry_ok(const mt_conv3d_t* p, int cfg);
-static bool conv_x16_ok(const mt_conv3d_t* p, int cfg) {
-  const int g_x16 = mt_sel3(p, MT_SEL_X16);
-  if (!g_x16) return false;
-  if (g_x16 == 1) {
-    const int nch = mt_cdiv(p->src[0].C, FCK) + (p->nsrc == 2 ? mt_cdiv(p->src[1].C, FCK) : 0);
-    if (p->Cout > 32 && nch < 8) return false;
-  }
-  return conv_x16_geometry_ok(p, cfg);
-}
 static bool conv_x16_geometry_ok(const mt_conv3d_t* p, int cfg) {
   if (cfg != 0 || p->mma != 1) return false;
   const int sd = conv_src_dtype(p);
-  if (!mt_is16(sd) || p->odtype != sd || !conv_out_pairs_ok(p)) return false;
+  if (!mt_is16(sd) || p->odtype != sd || !out_pairs_aligned(p)) return false;
   if (p->csplit < p->Cout || p->osD > 0 || p->bstats.y != nullptr) return false;
   if (!(p->KH == 3 && p->KW == 3 && (p->KD == 3 || p->KD == 1) && p->SD == 1 && p->SH == 1 && p->SW == 1 && p->PH == 1 && p->PW == 1 &&
         p->PD == (p->KD == 3 ? 1 : 0) && p->dilD == 1 && p->dilH == 1 && p->dilW == 1)) return false;
@@ -2277,32 +2008,22 @@ static bool conv_x16_geometry_ok(const mt_conv3d_t* p, int cfg) {
   if ((long)p->N * mt_cdiv(p->Do, 4) * mt_cdiv(p->Ho, 4) * mt_cdiv(p->Wo, 32) * mt_cdiv(p->Cout, 32) >= 2147483647L) return false;
   return true;
 }
-static int launch_x16(const mt_conv3d_t* p, hipStream_t st) {
-  X16Params P;
-  P.c = *p;
-  if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
-  P.tilesD = mt_cdiv(p->Do, 4); P.tilesH = mt_cdiv(p->Ho, 4); P.tilesW = mt_cdiv(p->Wo, 32);
-  P.nsb = P.tilesD * P.tilesH * P.tilesW;
-  P.ncot = mt_cdiv(p->Cout, 32);
-  P.nitems = p->N * P.nsb * P.ncot;
-  P.nchunks = mt_build_chunks(p->src[0].C, p->nsrc == 2 ? p->src[1].C : 0, FCK, P.chunk);
-  MT_REQUIRE(P.nchunks > 0, "conv3d (x16): too many channel chunks (Cin=%d)", p->Cin);
-  P.npairs = 0;
-  for (int i = 0; i < P.nchunks; ++P.npairs) {
-    const bool two = i + 1 < P.nchunks && P.chunk[i + 1].src == P.chunk[i].src && P.chunk[i + 1].c0 == P.chunk[i].c0 + 16;
-    P.pair[P.npairs][0] = (short)i; P.pair[P.npairs][1] = (short)(two ? i + 1 : -1);
-    i += two ? 2 : 1;
+static bool conv_x16_ok(const mt_conv3d_t* p, int cfg) {
+  const int g_x16 = mt_sel3(p, MT_SEL_X16);
+  if (!g_x16) return false;
+  if (g_x16 == 1) {
+    const int nch = mt_cdiv(p->src[0].C, FCK) + (p->nsrc == 2 ? mt_cdiv(p->src[1].C, FCK) : 0);
+    if (p->Cout > 32 && nch < 8) return false;
   }
-  P.nwg = mt_conv_x16_workgroups(P.nitems);
-  if (p->max_workgroups > 0 && P.nwg > p->max_workgroups) P.nwg = p->max_workgroups;
-  return mt_launch_conv_x16(P, p->KD, conv_src_dtype(p), st);
+  return conv_x16_geometry_ok(p, cfg);
 }
 
 // Packed patch geometry of the persistent kernel: a task's linear offset (ld*Hi + lh)*Wi + lw with ld, lh <= 5 and lw <= 17 lives
 // in bits 0-19 of a table entry, so its maximum (5*Hi + 5)*Wi + 17 must stay below 2^20 (beyond that the offset would spill into
 // the ld bits); larger planes take the direct kernels.
-// MT_SEL_BWDW_CW as the legacy value: most cout tiles per workgroup (1 | 2 | 4), + 100 = also where a workgroup walks few tiles
 static bool wino_persist_geometry_ok(const mt_conv3d_t* p) { return (5.0 * p->Hi + 5.0) * p->Wi + 17.0 < 1048576.0; }
+// Winograd eligibility: FAST geometry, 8-byte channel pairs in every source, one destination, enough workgroups to fill
+// the chip with 4x4x16 tiles and enough input channels to amortise the transforms
 static bool conv_wino_ok(const mt_conv3d_t* p) {
   const int use = mt_sel3(p, MT_SEL_WINO);
   if (!use) return false;
@@ -2313,62 +2034,21 @@ static bool conv_wino_ok(const mt_conv3d_t* p) {
   const long wgs = (long)p->N * mt_cdiv(p->Do, 4) * mt_cdiv(p->Ho, 4) * mt_cdiv(p->Wo, 16) * mt_cdiv(p->Cout, 32);
   return wgs >= 256 || use == 2;          // MT_SEL_FORCE in the MT_SEL_WINO field forces it (tests on small shapes)
 }
-// mt_bwd_stats_t is implemented in the epilogue of the persistent register-staged Winograd kernel (conv_wino8p_kernel)
+// mt_bwd_stats_t is implemented in the epilogue of the persistent register-staged Winograd kernel (conv_wino8pb_kernel)
 static bool wino_serves_bwd_stats(const mt_conv3d_t* p) {
   return wino_persist_geometry_ok(p);
-}
-static int launch_wino(const mt_conv3d_t* p, hipStream_t st) {
-  MT_REQUIRE(p->bstats.y == nullptr || (wino_serves_bwd_stats(p) && p->stats_part != nullptr && p->bstats.mean && p->bstats.rstd &&
-                                        p->bstats.c0 >= 0 && p->bstats.C > 0 && p->bstats.c0 + p->bstats.C <= p->Cout),
-             "conv3d: bstats set on a problem this kernel does not compute them for (ask mt_conv3d_bwd_stats_supported)");
-  ConvKParams P;
-  P.c = *p;
-  if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
-  P.tilesD = mt_cdiv(p->Do, 4); P.tilesH = mt_cdiv(p->Ho, 4); P.tilesW = mt_cdiv(p->Wo, 16);
-  P.nsb = P.tilesD * P.tilesH * P.tilesW;
-  P.ntaps = 27; P.dbg = 0; P.stagger = 0;
-  P.nchunks = mt_build_chunks(p->src[0].C, p->nsrc == 2 ? p->src[1].C : 0, WCK, P.chunk);
-  MT_REQUIRE(P.nchunks > 0, "conv3d: too many channel chunks for the Winograd kernel (Cin=%d)", p->Cin);
-  const int devid = mt_current_device();
-  const size_t l8 = (size_t)(2 * W_RAWF + W_VF) * sizeof(float) + 11 * 256 * 4;          // two raw patches + V + the patch-geometry table
-  // one resident workgroup per CU (126 KiB of LDS each): NW workers per output-channel tile walk over the spatial tiles
-  const int T = P.nsb * p->N, nct = mt_cdiv(p->Cout, 32);
-  int nw = mt_device_cus(devid) / nct; if (nw < 1) nw = 1; if (nw > T) nw = T;
-  if (p->max_workgroups > 0 && nw > p->max_workgroups) nw = p->max_workgroups;       // tests: few workers, many tiles each
-  if (p->bstats.y != nullptr) {
-    static std::atomic<uint64_t> attrb{0};
-    if (mt_device_pending(attrb, devid)) {
-      hipError_t e = hipFuncSetAttribute((const void*)conv_wino8pb_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l8);
-      if (e != hipSuccess) { mt_set_error("conv3d: cannot raise dynamic LDS to %zu: %s", l8, hipGetErrorString(e)); return MT_EHIP; }
-      mt_mark_device_done(attrb, devid);
-    }
-    hipLaunchKernelGGL(conv_wino8pb_kernel, dim3((unsigned)nw, (unsigned)nct, 1), dim3(512), l8, st, P);
-    MT_CHECK_LAUNCH("conv3d_wino8pb");
-    return MT_OK;
-  }
-  static std::atomic<uint64_t> attrp{0};
-  if (mt_device_pending(attrp, devid)) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wino8p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l8);
-    if (e != hipSuccess) { mt_set_error("conv3d: cannot raise dynamic LDS to %zu: %s", l8, hipGetErrorString(e)); return MT_EHIP; }
-    mt_mark_device_done(attrp, devid);
-  }
-  hipLaunchKernelGGL(conv_wino8p_kernel, dim3((unsigned)nw, (unsigned)nct, 1), dim3(512), l8, st, P);
-  MT_CHECK_LAUNCH("conv3d_wino8p");
-  return MT_OK;
 }
 
 // kernel == stride, pad 0, one plain destination, no statistics: every output owns its input block (conv_gather_kernel)
 static bool conv_gather_ok(const mt_conv3d_t* p) {
-  constexpr int use = 1;
-  if (!use || p->nsrc != 1 || p->csplit < p->Cout || p->osD > 0 || p->stats_part != nullptr) return false;
+  if (p->nsrc != 1 || p->csplit < p->Cout || p->osD > 0 || p->stats_part != nullptr) return false;
   if (!(p->KD == p->SD && p->KH == p->SH && p->KW == p->SW && p->PD == 0 && p->PH == 0 && p->PW == 0)) return false;
   if (!(p->dilD == 1 && p->dilH == 1 && p->dilW == 1)) return false;
   if ((double)p->Do * p->Ho * p->Wo * p->ocs0 * 4.0 >= 2147483648.0) return false;
   return true;
 }
 static bool gather_use_bf16(const mt_conv3d_t* p) {          // mixed precision: a bf16 gradient without a lazy activation
-  constexpr int use = 1;
-  return use && p->mma == 1 && p->src[0].dtype == MT_BF16 && p->src[0].scale == nullptr && !(p->src[0].cs & 1) && !(((uintptr_t)p->src[0].ptr) & 3);
+  return p->mma == 1 && p->src[0].dtype == MT_BF16 && p->src[0].scale == nullptr && !(p->src[0].cs & 1) && !(((uintptr_t)p->src[0].ptr) & 3);
 }
 // two cout tiles per wave: fp32 on both sides, at least two tiles, and a grid that still fills the chip four times over (measured, tools/bench_gather.py:
 // 30 -> 60 @ 2x24x96x96 outputs 280 -> 231 us (218 with the chunk pairs and the wide epilogue), 60 -> 120 @ 12x48x48 97 -> 99, 120 -> 240 @ 6x24x24 70 -> 83 -
@@ -2381,39 +2061,9 @@ static bool gather_nt2(const mt_conv3d_t* p) {
   const long wgs = (((long)p->Do * p->Ho * p->Wo + 127) / 128) * p->N * mt_cdiv(mt_cdiv(p->Cout, 32), 2);
   return wgs >= 4L * mt_device_cus(mt_current_device());
 }
-static int launch_gather(const mt_conv3d_t* p, hipStream_t st) {
-  ConvKParams P;
-  P.c = *p;
-  P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0;
-  P.ntaps = p->KD * p->KH * p->KW; P.dbg = 0; P.stagger = 0;
-  P.nchunks = mt_build_chunks(p->src[0].C, 0, FCK, P.chunk);
-  MT_REQUIRE(P.nchunks > 0, "conv3d: too many channel chunks (Cin=%d)", p->Cin);
-  const long V = (long)p->Do * p->Ho * p->Wo;
-  P.tilesD = P.tilesH = P.tilesW = 1; P.nsb = (int)((V + 127) / 128);
-  dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(p->Cout, 32), 1);
-  const mt_src_t& S = p->src[0];
-  // 16-byte loads at any alignment (dword-aligned dwordx4 buffer loads are legal and range-checked per dword: tools/ubench/oob128.hip)
-  // (the <2> and <1> instances below are unreachable; they stay until the device code itself is cleaned up)
-  const int vec = 4;
-  // gradients: bf16 -> bf16 (backward-data of a transposed convolution between two 16-bit levels), bf16 -> fp32, fp32 -> bf16
-  if (gather_use_bf16(p) && p->odtype == MT_BF16) hipLaunchKernelGGL((conv_gather_kernel<4, MT_BF16, MT_BF16, true>), grid, dim3(256), 0, st, P);
-  else if (gather_use_bf16(p)) hipLaunchKernelGGL((conv_gather_kernel<4, MT_BF16, MT_F32, true>), grid, dim3(256), 0, st, P);
-  else if (S.dtype == MT_BF16 && p->odtype == MT_BF16) hipLaunchKernelGGL((conv_gather_kernel<4, MT_BF16, MT_BF16>), grid, dim3(256), 0, st, P);
-  else if (S.dtype == MT_BF16) hipLaunchKernelGGL((conv_gather_kernel<4, MT_BF16, MT_F32>), grid, dim3(256), 0, st, P);
-  else if (p->odtype == MT_BF16) hipLaunchKernelGGL((conv_gather_kernel<4, MT_F32, MT_BF16>), grid, dim3(256), 0, st, P);
-  else if (vec == 4 && gather_nt2(p)) {
-    grid.y = (unsigned)mt_cdiv(mt_cdiv(p->Cout, 32), 2);
-    hipLaunchKernelGGL((conv_gather_kernel<4, MT_F32, MT_F32, false, 2>), grid, dim3(256), 0, st, P);
-  }
-  else if (vec == 4) hipLaunchKernelGGL(conv_gather_kernel<4>, grid, dim3(256), 0, st, P);
-  else if (vec == 2) hipLaunchKernelGGL(conv_gather_kernel<2>, grid, dim3(256), 0, st, P);
-  else hipLaunchKernelGGL(conv_gather_kernel<1>, grid, dim3(256), 0, st, P);
-  MT_CHECK_LAUNCH("conv3d_gather");
-  return MT_OK;
-}
 
 static size_t rt_lds(const ConvCfg& g, const mt_conv3d_t* p) {
-  int TD = g.TD, TH = (32 / g.MW) * g.RH, TW = g.MW;
+  int TD, TH, TW; cfg_tile(g, &TD, &TH, &TW);
   const size_t LD = (TD - 1) * p->SD + p->KD, LH = (TH - 1) * p->SH + p->KH, LW = (TW - 1) * p->SW + p->KW;
   size_t b = LD * LH * LW * FCKP * sizeof(float);
   return b < 1024 ? 1024 : b;
@@ -2434,273 +2084,525 @@ static int pick_rt_cfg(const mt_conv3d_t* p) {
     const ConvCfg& g = kCfgs[i];
     const size_t l = rt_lds(g, p);
     if (l > 160 * 1024) continue;
-    int TD = g.TD, TH = (32 / g.MW) * g.RH, TW = g.MW;
+    int TD, TH, TW; cfg_tile(g, &TD, &TH, &TW);
     double cost = (double)mt_cdiv(p->Do, TD) * TD * mt_cdiv(p->Ho, TH) * TH * mt_cdiv(p->Wo, TW) * TW;
     if (l > 80 * 1024) cost *= 1.15;
     if (cost < bestcost - 1e-9) { bestcost = cost; best = i; }
   }
   return best;
 }
-template <int MW, int RH, int TD, int VEC>
-static int launch_rt(const mt_conv3d_t* p, const ConvCfg& g, hipStream_t st) {
-  ConvKParams P;
-  P.c = *p;
-  if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
-  int TDv = g.TD, TH = (32 / g.MW) * g.RH, TW = g.MW;
-  P.tilesD = mt_cdiv(p->Do, TDv); P.tilesH = mt_cdiv(p->Ho, TH); P.tilesW = mt_cdiv(p->Wo, TW);
-  P.nsb = P.tilesD * P.tilesH * P.tilesW;
-  P.ntaps = p->KD * p->KH * p->KW; P.dbg = 0; P.stagger = 0;
-  P.nchunks = mt_build_chunks(p->src[0].C, p->nsrc == 2 ? p->src[1].C : 0, FCK, P.chunk);
-  MT_REQUIRE(P.nchunks > 0, "conv3d: too many channel chunks (Cin=%d)", p->Cin);
-  const size_t ldsb = rt_lds(g, p);
-  dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(p->Cout, 32), 1);
-  auto kfn = conv_rt_kernel<MW, RH, TD, VEC>;
-  if (ldsb > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    if (e != hipSuccess) { mt_set_error("conv3d: cannot raise dynamic LDS to %zu: %s", ldsb, hipGetErrorString(e)); return MT_EHIP; }
+
+// ---- the one dispatch decision of mt_conv3d_fwd.  conv_resolve is the only reader of the eligibility predicates above; the queries, the
+// kernel name and the launchers are functions of the ConvChoice it returns (and of plain fields of p).
+enum ConvFamily { CONV_NONE = 0, CONV_STEM, CONV_WINO, CONV_WINO_B, CONV_FAST, CONV_TAPSPLIT, CONV_FAST_STRIDED, CONV_BF16, CONV_X16, CONV_GATHER,
+                  CONV_RT, CONV_GENERIC };
+struct ConvChoice {
+  int family;        // CONV_NONE: no tile configuration of the generic kernel fits LDS
+  ConvCfg g;         // tile configuration of the tiled kernels (conv_tile for the spatial tile of every family)
+  int ck;            // channels per chunk = the ck argument of mt_pack_conv_weights
+  // the template instance: staging width, storage types of sources and destination, matrix type, 16-bit matrix inputs
+  int vec, xs, os, mty;
+  bool m16;
+  bool nt2;          // conv_gather_kernel: two cout tiles per wave
+  bool bstats;       // the Winograd families: mt_bwd_stats_t is served (CONV_WINO_B computes it)
+  bool fast;         // FAST flag of conv_fwd_kernel
+};
+static ConvChoice conv_resolve(const mt_conv3d_t* p) {
+  ConvChoice c = {};
+  const int cfg = pick_cfg(p), sd = conv_src_dtype(p);
+  c.family = cfg < 0 ? CONV_NONE : CONV_GENERIC;
+  if (cfg >= 0) c.g = kCfgs[cfg];
+  c.ck = c.g.CK; c.vec = conv_fast_vec(p); c.xs = MT_F32; c.os = MT_F32; c.mty = MT_BF16;
+  // the strided and tap-split kernels in mixed precision: a 16-bit source multiplies as its own type (fp16 activations: the forward pass;
+  // bf16: gradients) and the destination has the source's type, or fp32 (a level the engine keeps in fp32); fp32 sources round to bf16
+  auto strided_instance = [&] {
+    c.m16 = strided_use_bf16(p);
+    if (c.m16 && sd > 0) { c.vec = 4; c.xs = sd; c.os = p->odtype == sd ? sd : MT_F32; c.mty = sd == MT_F16 ? MT_F16 : MT_BF16; }
+  };
+  if (p->mma == 1) {                      // 16-bit matrix inputs where the bf16 kernel serves the problem; fp32 kernels elsewhere
+    const int bc = conv_bf16_cfg(p);
+    if (bc >= 0) {
+      // storage: all fp32 (bf16 matrix type), all bf16 (backward-data over gradients) or all fp16 (forward over activations: fp16 matrix
+      // type); 16-bit sources are read as 8-byte groups of four channels (fp32: 16-byte staging loads measured slower, 0.409 vs 0.372 ms
+      // on 32->32), 16-bit destinations written as channel-pair dwords
+      c.family = conv_x16_ok(p, bc) ? CONV_X16 : CONV_BF16;
+      c.g = kBfCfgs[bc]; c.ck = FCK; c.m16 = true;
+      c.vec = sd > 0 ? 4 : 2; c.xs = c.os = sd > 0 ? sd : MT_F32; c.mty = sd == MT_F16 ? MT_F16 : MT_BF16;
+      return c;
+    }
   }
-  hipLaunchKernelGGL(kfn, grid, dim3(256), ldsb, st, P);
-  MT_CHECK_LAUNCH("conv3d_rt");
-  return MT_OK;
+  const bool fast = conv_is_fast(p), small = cfg >= 0 && cfg <= 2 && p->osD <= 0;
+  const bool out31 = (double)p->Do * p->Ho * p->Wo * p->ocs0 * 4.0 < 2147483648.0;         // 31-bit store offsets per sample
+  if (fast && p->osD <= 0 && p->nsrc == 1 && p->Cin == 1 && p->csplit >= p->Cout && out31) {
+    c.family = CONV_STEM; c.g = kCfgs[0]; c.ck = c.g.CK; c.os = p->odtype;
+    return c;
+  }
+  if (fast && small && conv_wino_ok(p)) {
+    c.bstats = wino_serves_bwd_stats(p);
+    c.family = p->bstats.y != nullptr ? CONV_WINO_B : CONV_WINO; c.ck = WCK;
+    return c;
+  }
+  if (fast && small) {
+    c.family = CONV_FAST;
+    // low-resolution stages: fewer than two workgroups per CU -> split the taps over the waves instead
+    int TD, TH, TW; cfg_tile(c.g, &TD, &TH, &TW);
+    const long wgs = (long)p->N * mt_cdiv(p->Do, TD) * mt_cdiv(p->Ho, TH) * mt_cdiv(p->Wo, TW) * mt_cdiv(p->Cout, 32);
+    if (mt_sel3(p, MT_SEL_TAPSPLIT) && wgs < 300 && p->csplit >= p->Cout && out31) { c.family = CONV_TAPSPLIT; strided_instance(); }
+    return c;
+  }
+  if (conv_is_133(p) && small && p->Cin >= 8) { c.family = CONV_FAST; return c; }      // compile-time taps instead of conv_rt
+  if (conv_fast_strided_ok(p)) {
+    c.family = CONV_FAST_STRIDED; c.g = kCfgs[0]; c.ck = c.g.CK;
+    strided_instance();
+    // fewer workgroups than CUs in the 2x4x8 x 64-channel tiling: one 32-voxel tile x 32 channels per workgroup, taps over the waves
+    // (instances: fp32 with 8-byte channel pairs, or 16-bit storage)
+    const int g_tapsplit = mt_sel3(p, MT_SEL_TAPSPLIT);
+    const long wgs = (long)p->N * mt_cdiv(p->Do, 2) * mt_cdiv(p->Ho, 4) * mt_cdiv(p->Wo, 8) * mt_cdiv(p->Cout, 64);
+    const bool inst = c.m16 ? mt_is16(sd) && (p->odtype == sd || p->odtype == MT_F32) : (sd == MT_F32 && p->odtype == MT_F32 && c.vec == 2);
+    if (g_tapsplit && (wgs < 256 || g_tapsplit >= 2) && inst) c.family = CONV_TAPSPLIT;
+    return c;
+  }
+  if (conv_rt_ok(p)) {
+    const int i = pick_rt_cfg(p);
+    if (i >= 0) {
+      c.family = CONV_RT; c.g = kCfgs[i]; c.ck = c.g.CK;
+      if (conv_gather_ok(p)) {           // gradients: bf16 -> bf16 (backward-data of a transposed convolution between two 16-bit levels), bf16 -> fp32, fp32 -> bf16
+        // 16-byte loads at any alignment (dword-aligned dwordx4 buffer loads are legal and range-checked per dword: tools/ubench/oob128.hip)
+        c.family = CONV_GATHER; c.ck = FCK; c.vec = 4; c.xs = p->src[0].dtype; c.os = p->odtype;
+        c.m16 = gather_use_bf16(p); c.nt2 = gather_nt2(p);
+      }
+      return c;
+    }
+  }
+  c.fast = fast && (cfg <= 3 || cfg == 6);
+  return c;
+}
+struct ConvTile { int D, H, W; };
+// spatial output tile of a workgroup (conv_gather_kernel walks 128 voxels in linear order and takes no statistics: the tile of its
+// conv_rt configuration only sizes mt_conv3d_stats_blocks, as before)
+static ConvTile conv_tile(const ConvChoice& c) {
+  switch (c.family) {
+    case CONV_FAST_STRIDED: return {2, 4, 8};
+    case CONV_TAPSPLIT: return {2, 4, 4};
+    case CONV_WINO: case CONV_WINO_B: return {4, 4, 16};
+    default: { ConvTile t; cfg_tile(c.g, &t.D, &t.H, &t.W); return t; }
+  }
 }
 
-template <int MW, int RH, int TD, int CK, bool FAST>
-static int launch_conv(const mt_conv3d_t* p, const ConvCfg& g, hipStream_t st) {
-  ConvKParams P;
-  P.c = *p;
-  if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
-  int TDv, TH, TW; cfg_tile(g, &TDv, &TH, &TW);
-  P.tilesD = mt_cdiv(p->Do, TDv); P.tilesH = mt_cdiv(p->Ho, TH); P.tilesW = mt_cdiv(p->Wo, TW);
-  P.nsb = P.tilesD * P.tilesH * P.tilesW;
-  P.ntaps = p->KD * p->KH * p->KW;
-  P.nchunks = mt_build_chunks(p->src[0].C, p->nsrc == 2 ? p->src[1].C : 0, CK, P.chunk);
-  MT_REQUIRE(P.nchunks > 0, "conv3d: too many channel chunks (Cin=%d, ck=%d)", p->Cin, CK);
-  {
-    constexpr int stagger_env = 0;
-    P.stagger = stagger_env;
-    constexpr int dbg_env = 0;
-    P.dbg = dbg_env;
-  }
-  const size_t ldsb = cfg_lds(g, p);
-  dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(p->Cout, 32), 1);
-  auto kfn = conv_fwd_kernel<MW, RH, TD, CK, FAST>;
-  if (ldsb > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    if (e != hipSuccess) { mt_set_error("conv3d: cannot raise dynamic LDS to %zu: %s", ldsb, hipGetErrorString(e)); return MT_EHIP; }
-  }
-  hipLaunchKernelGGL(kfn, grid, dim3(256), ldsb, st, P);
-  MT_CHECK_LAUNCH("conv3d_fwd");
-  return MT_OK;
+extern "C" int mt_conv3d_ck(const mt_conv3d_t* p) {
+  const ConvChoice c = conv_resolve(p);
+  return c.family == CONV_NONE ? -1 : c.ck;
 }
-
-// name of the device kernel mt_conv3d_fwd will launch for this problem (as rocprofv3 prints it) — lets the benchmark
-// attribute per-launch timings to the same kernel names the profiler reports
-extern "C" int mt_conv3d_kernel_name(const mt_conv3d_t* p, char* buf, size_t n) {
-  if (p == nullptr || buf == nullptr || n == 0) return MT_EINVAL;
-  const ConvPlan pl = conv_plan(p);
-  const int i = pl.cfg;
-  if (i < 0) return MT_EINVAL;
-  if (pl.kind == CONV_BF16 && conv_x16_ok(p, i)) { snprintf(buf, n, "conv_x16_kernel<%d, %d>", p->KD, conv_src_dtype(p)); return MT_OK; }
-  if (pl.kind == CONV_BF16) {
-    // the instance launch_bf16 picks, as the profiler prints it: <MW, RH, TD, VEC, NT, NW, KD, XS, OS, MTY>
-    const int sd = conv_src_dtype(p);
-    snprintf(buf, n, "conv_bf16_kernel<%d, %d, %d, %d, 1, 4, %d, %d, %d, %d>", kBfCfgs[i].MW, kBfCfgs[i].RH, kBfCfgs[i].TD, sd > 0 ? 4 : conv_bf16_vec(p), p->KD,
-             sd > 0 ? sd : 0, sd > 0 ? sd : 0, sd == MT_F16 ? MT_F16 : MT_BF16);
-    return MT_OK;
-  }
-  const ConvCfg& g = kCfgs[i];
-  const bool fast = conv_is_fast(p);
-  if (pl.kind == CONV_FAST)
-    snprintf(buf, n, "conv_fast_kernel<%d, %d, %d, %d, %d>", g.MW, g.RH, g.TD, conv_fast_vec(p), p->KD);
-  else if (pl.kind == CONV_TAPSPLIT)
-  {
-    const int sd = conv_src_dtype(p);
-    if (p->SH == 2 && strided_use_bf16(p)) snprintf(buf, n, "conv_tapsplit_kernel<4, true, %d, %d, %d, %d, 2, 2>", sd, p->odtype == sd ? sd : 0, sd == MT_F16 ? MT_F16 : MT_BF16, p->SD);
-    else if (p->SH == 2) snprintf(buf, n, "conv_tapsplit_kernel<2, false, 0, 0, 1, %d, 2, 2>", p->SD);
-    else if (strided_use_bf16(p) && sd > 0) snprintf(buf, n, "conv_tapsplit_kernel<4, true, %d, %d, %d>", sd, p->odtype == sd ? sd : 0, sd == MT_F16 ? MT_F16 : MT_BF16);
-    else snprintf(buf, n, strided_use_bf16(p) ? "conv_tapsplit_kernel<%d, true, 0, 0, 1>" : "conv_tapsplit_kernel<%d, false, 0, 0, 1>", conv_fast_vec(p));
-  }
-  else if (pl.kind == CONV_STEM)
-    snprintf(buf, n, "conv_stem_kernel<%d>", p->odtype);
-  else if (pl.kind == CONV_WINO)
-    snprintf(buf, n, p->bstats.y != nullptr ? "conv_wino8pb_kernel" : "conv_wino8p_kernel");
-  else if (pl.kind == CONV_FAST_STRIDED)
-  {
-    const int sd = conv_src_dtype(p);
-    if (strided_use_bf16(p) && sd > 0)
-      snprintf(buf, n, "conv_fast_strided_kernel<%d, %d, %d, 4, true, %d, %d, %d>", p->SD, p->SH, p->SW, sd, p->odtype == sd ? sd : 0, sd == MT_F16 ? MT_F16 : MT_BF16);
-    else
-      snprintf(buf, n, strided_use_bf16(p) ? "conv_fast_strided_kernel<%d, %d, %d, %d, true, 0, 0, 1>" : "conv_fast_strided_kernel<%d, %d, %d, %d, false, 0, 0, 1>",
-               p->SD, p->SH, p->SW, conv_fast_vec(p));
-  }
-  else if (pl.kind == CONV_RT && conv_gather_ok(p))
-    snprintf(buf, n, gather_use_bf16(p) ? "conv_gather_kernel<4, %d, %d, true>" : gather_nt2(p) ? "conv_gather_kernel<4, %d, %d, false, 2>" : "conv_gather_kernel<4, %d, %d>", p->src[0].dtype, p->odtype);
-  else if (pl.kind == CONV_RT)
-    snprintf(buf, n, "conv_rt_kernel<%d, %d, %d, %d>", g.MW, g.RH, g.TD, conv_fast_vec(p));
-  else
-    snprintf(buf, n, "conv_fwd_kernel<%d, %d, %d, %d, %s>", g.MW, g.RH, g.TD, g.CK, (fast && (i <= 3 || i == 6)) ? "true" : "false");
-  return MT_OK;
+extern "C" int mt_conv3d_pack_layout(const mt_conv3d_t* p) {      // layout argument of mt_pack_conv_weights for this problem
+  const ConvChoice c = conv_resolve(p);
+  if (c.m16) return c.mty == MT_F16 ? 4 : 3;         // fp16 sources multiply as fp16, everything else as bf16
+  return (c.family == CONV_WINO || c.family == CONV_WINO_B) ? 2 : 1;
 }
-
+extern "C" int mt_conv3d_stats_blocks(const mt_conv3d_t* p) {
+  const ConvChoice c = conv_resolve(p);
+  if (c.family == CONV_NONE) return -1;
+  const ConvTile t = conv_tile(c);
+  return mt_cdiv(p->Do, t.D) * mt_cdiv(p->Ho, t.H) * mt_cdiv(p->Wo, t.W);
+}
 extern "C" int mt_conv3d_bwd_stats_supported(const mt_conv3d_t* p) {
   if (p == nullptr || conv_validate(p) != MT_OK) return 0;
-  const ConvPlan pl = conv_plan(p);
-  return (pl.cfg >= 0 && pl.kind == CONV_WINO && wino_serves_bwd_stats(p)) ? 1 : 0;
+  return conv_resolve(p).bstats ? 1 : 0;
 }
 
 // Storage types (mt_src_t.dtype, mt_conv3d_t.odtype): 1 when the kernel that serves p reads / writes them natively.  All-fp32 is
 // always supported; 16-bit storage is taken by the 16-bit matrix kernels (p->mma == 1): conv_bf16_kernel with ONE 16-bit type on all
 // operands (fp16: the forward pass, fp16 products; bf16: backward-data, bf16 products), the strided stage kernel with 16-bit sources
 // (destination of the same type, or fp32).  Elsewhere the caller converts with mt_cast.
-extern "C" int mt_conv3d_io_supported(const mt_conv3d_t* p) {
-  if (p == nullptr) return 0;
+static int conv_io_served(const mt_conv3d_t* p, const ConvChoice& c) {
   const int sd = conv_src_dtype(p);
   if (sd < 0 || !mt_dtype_ok(p->odtype)) return 0;
   if (sd == MT_F32 && p->odtype == MT_F32) return 1;
   if (p->bstats.y != nullptr) return 0;
-  const ConvPlan pl = conv_plan(p);
-  if (pl.cfg < 0) return 0;
-  if (pl.kind == CONV_BF16) return (mt_is16(sd) && p->odtype == sd && conv_out_pairs_ok(p)) ? 1 : 0;
-  if ((pl.kind == CONV_FAST_STRIDED || pl.kind == CONV_TAPSPLIT) && strided_use_bf16(p))
-    return (mt_is16(sd) && (p->odtype == MT_F32 || (p->odtype == sd && conv_out_pairs_ok(p)))) ? 1 : 0;
-  if (pl.kind == CONV_STEM) return (sd == MT_F32 && conv_out_pairs_ok(p)) ? 1 : 0;          // fp32 network input, any output type
-  if (pl.kind == CONV_RT && conv_gather_ok(p)) {                                             // gradients: fp32 / bf16 on either side
-    if (sd == MT_F16 || p->odtype == MT_F16) return 0;
-    if (sd == MT_BF16 && ((p->src[0].cs & 1) || (((uintptr_t)p->src[0].ptr) & 3))) return 0;
-    return (p->odtype == MT_F32 || conv_out_pairs_ok(p)) ? 1 : 0;
+  switch (c.family) {
+    case CONV_BF16: case CONV_X16: return (mt_is16(sd) && p->odtype == sd && out_pairs_aligned(p)) ? 1 : 0;
+    case CONV_FAST_STRIDED: case CONV_TAPSPLIT:
+      return (c.m16 && mt_is16(sd) && (p->odtype == MT_F32 || (p->odtype == sd && out_pairs_aligned(p)))) ? 1 : 0;
+    case CONV_STEM: return (sd == MT_F32 && out_pairs_aligned(p)) ? 1 : 0;          // fp32 network input, any output type
+    case CONV_GATHER:                                                                // gradients: fp32 / bf16 on either side
+      if (sd == MT_F16 || p->odtype == MT_F16) return 0;
+      if (sd == MT_BF16 && ((p->src[0].cs & 1) || (((uintptr_t)p->src[0].ptr) & 3))) return 0;
+      return (p->odtype == MT_F32 || out_pairs_aligned(p)) ? 1 : 0;
+    default: return 0;
   }
-  return 0;
+}
+extern "C" int mt_conv3d_io_supported(const mt_conv3d_t* p) {
+  if (p == nullptr) return 0;
+  return conv_io_served(p, conv_resolve(p));
+}
+
+// name of the device kernel mt_conv3d_fwd will launch for this problem (as rocprofv3 prints it) — lets the benchmark
+// attribute per-launch timings to the same kernel names the profiler reports
+extern "C" int mt_conv3d_kernel_name(const mt_conv3d_t* p, char* buf, size_t n) {
+  if (p == nullptr || buf == nullptr || n == 0) return MT_EINVAL;
+  const ConvChoice c = conv_resolve(p);
+  const ConvCfg& g = c.g;
+  const char* b = c.m16 ? "true" : "false";
+  switch (c.family) {
+    case CONV_STEM: snprintf(buf, n, "conv_stem_kernel<%d>", c.os); break;
+    case CONV_WINO: snprintf(buf, n, "conv_wino8p_kernel"); break;
+    case CONV_WINO_B: snprintf(buf, n, "conv_wino8pb_kernel"); break;
+    case CONV_FAST: snprintf(buf, n, "conv_fast_kernel<%d, %d, %d, %d, %d>", g.MW, g.RH, g.TD, c.vec, p->KD); break;
+    case CONV_TAPSPLIT:
+      if (p->SH == 2) snprintf(buf, n, "conv_tapsplit_kernel<%d, %s, %d, %d, %d, %d, 2, 2>", c.vec, b, c.xs, c.os, c.mty, p->SD);
+      else snprintf(buf, n, "conv_tapsplit_kernel<%d, %s, %d, %d, %d>", c.vec, b, c.xs, c.os, c.mty);
+      break;
+    case CONV_FAST_STRIDED: snprintf(buf, n, "conv_fast_strided_kernel<%d, %d, %d, %d, %s, %d, %d, %d>", p->SD, p->SH, p->SW, c.vec, b, c.xs, c.os, c.mty); break;
+    case CONV_BF16: snprintf(buf, n, "conv_bf16_kernel<%d, %d, %d, %d, 1, 4, %d, %d, %d, %d>", g.MW, g.RH, g.TD, c.vec, p->KD, c.xs, c.os, c.mty); break;   // <MW, RH, TD, VEC, NT, NW, KD, XS, OS, MTY>
+    case CONV_X16: snprintf(buf, n, "conv_x16_kernel<%d, %d>", p->KD, c.xs); break;
+    case CONV_GATHER: snprintf(buf, n, c.m16 ? "conv_gather_kernel<%d, %d, %d, true>" : c.nt2 ? "conv_gather_kernel<%d, %d, %d, false, 2>" : "conv_gather_kernel<%d, %d, %d>", c.vec, c.xs, c.os); break;
+    case CONV_RT: snprintf(buf, n, "conv_rt_kernel<%d, %d, %d, %d>", g.MW, g.RH, g.TD, c.vec); break;
+    case CONV_GENERIC: snprintf(buf, n, "conv_fwd_kernel<%d, %d, %d, %d, %s>", g.MW, g.RH, g.TD, g.CK, c.fast ? "true" : "false"); break;
+    default: return MT_EINVAL;
+  }
+  return MT_OK;
+}
+
+// ---- launchers: each switches from the choice's runtime values to the template instance
+// kernel arguments of a tiled launch: the problem (a single source aliased into the empty second slot), the tile counts over the output and the channel chunks
+static int conv_fill(ConvKParams& P, const mt_conv3d_t* p, const ConvTile& t, int ntaps, int ck) {
+  P.c = *p;
+  if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
+  P.tilesD = mt_cdiv(p->Do, t.D); P.tilesH = mt_cdiv(p->Ho, t.H); P.tilesW = mt_cdiv(p->Wo, t.W);
+  P.nsb = P.tilesD * P.tilesH * P.tilesW;
+  P.ntaps = ntaps; P.dbg = 0; P.stagger = 0;
+  P.nchunks = mt_build_chunks(p->src[0].C, p->nsrc == 2 ? p->src[1].C : 0, ck, P.chunk);
+  MT_REQUIRE(P.nchunks > 0, "conv3d: too many channel chunks (Cin=%d, ck=%d)", p->Cin, ck);
+  return MT_OK;
+}
+// launch with `ldsb` bytes of dynamic LDS, raising the kernel's limit where that exceeds the default 64 KiB
+template <class K>
+static int conv_launch_lds(K kfn, dim3 grid, dim3 block, size_t ldsb, hipStream_t st, const ConvKParams& P, const char* what) {
+  if (ldsb > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
+    if (e != hipSuccess) { mt_set_error("conv3d: cannot raise dynamic LDS to %zu: %s", ldsb, hipGetErrorString(e)); return MT_EHIP; }
+  }
+  hipLaunchKernelGGL(kfn, grid, block, ldsb, st, P);
+  MT_CHECK_LAUNCH(what);
+  return MT_OK;
+}
+static dim3 conv_grid(const ConvKParams& P, int cout_per_wg) {
+  return dim3((unsigned)(P.nsb * P.c.N), (unsigned)mt_cdiv(P.c.Cout, cout_per_wg), 1);
+}
+
+static int launch_fast(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  ConvKParams P;
+  if (int rc = conv_fill(P, p, conv_tile(c), p->KD * 9, FCK)) return rc;
+#define MT_F_INST(MW_, RH_, TD_, VEC_, KD_) \
+  conv_launch_lds(conv_fast_kernel<MW_, RH_, TD_, VEC_, KD_>, conv_grid(P, 32), dim3(256), stage_lds_bytes<TD_ + KD_ - 1, (32 / MW_) * RH_ + 2, MW_ + 2, VEC_>(), st, P, "conv3d_fast")
+#define MT_F_CASE(MW_, RH_, TD_)                                                                                           \
+  if (c.g.MW == MW_) {                                                                                                     \
+    if (p->KD == 1) return c.vec == 2 ? MT_F_INST(MW_, RH_, TD_, 2, 1) : MT_F_INST(MW_, RH_, TD_, 1, 1);                   \
+    return c.vec == 2 ? MT_F_INST(MW_, RH_, TD_, 2, 3) : MT_F_INST(MW_, RH_, TD_, 1, 3);                                   \
+  }
+  MT_F_CASE(32, 4, 2)
+  MT_F_CASE(16, 2, 2)
+  MT_F_CASE(8, 2, 2)
+#undef MT_F_CASE
+#undef MT_F_INST
+  return MT_EINVAL;
+}
+
+// the 16-bit instances of the strided and tap-split kernels: (source, destination, matrix type) = (fp16, fp16 | fp32, fp16), (bf16, bf16 | fp32, bf16)
+#define MT_IO16_SWITCH(c_, LAUNCH_)                                                        \
+  do {                                                                                     \
+    if (c_.xs == MT_F16 && c_.os == MT_F16) LAUNCH_(MT_F16, MT_F16, MT_F16);               \
+    else if (c_.xs == MT_F16) LAUNCH_(MT_F16, MT_F32, MT_F16);                             \
+    else if (c_.os == MT_BF16) LAUNCH_(MT_BF16, MT_BF16, MT_BF16);                         \
+    else LAUNCH_(MT_BF16, MT_F32, MT_BF16);                                                \
+  } while (0)
+
+template <int SD>
+static int launch_fast_strided_t(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  constexpr int TD = 2, TH = 4, TW = 8, LD = (TD - 1) * SD + 3, LH = (TH - 1) * 2 + 3, LW = (TW - 1) * 2 + 3;
+  ConvKParams P;
+  if (int rc = conv_fill(P, p, conv_tile(c), 27, FCK)) return rc;
+  const dim3 grid = conv_grid(P, 64);
+#define MT_FS_LAUNCH(XS_, OS_, MTY_) hipLaunchKernelGGL((conv_fast_strided_kernel<SD, 2, 2, 4, true, XS_, OS_, MTY_>), grid, dim3(256), (bstage_lds_bytes<LD, LH, LW, 4, 4>()), st, P)
+  if (c.m16 && c.vec == 4) MT_IO16_SWITCH(c, MT_FS_LAUNCH);
+  else if (c.m16) hipLaunchKernelGGL((conv_fast_strided_kernel<SD, 2, 2, 2, true, MT_F32, MT_F32, MT_BF16>), grid, dim3(256), (bstage_lds_bytes<LD, LH, LW, 2, 4>()), st, P);
+  else if (c.vec == 2) hipLaunchKernelGGL((conv_fast_strided_kernel<SD, 2, 2, 2>), grid, dim3(256), (stage_lds_bytes<LD, LH, LW, 2>()), st, P);
+  else return conv_launch_lds(conv_fast_strided_kernel<SD, 2, 2, 1>, grid, dim3(256), stage_lds_bytes<LD, LH, LW, 1>(), st, P, "conv3d_fast_strided");
+#undef MT_FS_LAUNCH
+  MT_CHECK_LAUNCH("conv3d_fast_strided");
+  return MT_OK;
+}
+
+// SD, S2: depth and in-plane stride.  The strided forms exist as the 16-bit instances and as fp32 with 8-byte channel pairs (conv_resolve
+// takes the tap-split kernel only there); stride 1 also stages fp32 as bf16 and single channels.
+template <int SD, int S2>
+static void launch_tapsplit_t(const ConvChoice& c, dim3 grid, hipStream_t st, const ConvKParams& P) {
+  constexpr int LD = SD + 3, LH = 3 * S2 + 3;        // staged extent of the 2 x 4 x 4 tile
+  size_t l = (size_t)4 * 16 * 64 * sizeof(float);    // at least the cross-wave reduction buffer
+#define MT_TS_LAUNCH(VEC_, BF_, XS_, OS_, MTY_) hipLaunchKernelGGL((conv_tapsplit_kernel<VEC_, BF_, XS_, OS_, MTY_, SD, S2, S2>), grid, dim3(256), l, st, P)
+#define MT_TS_LAUNCH16(XS_, OS_, MTY_) MT_TS_LAUNCH(4, true, XS_, OS_, MTY_)
+  if (c.m16 && c.vec == 4) {
+    l = std::max(l, bstage_lds_bytes<LD, LH, LH, 4, 4>());
+    MT_IO16_SWITCH(c, MT_TS_LAUNCH16);
+  } else if (!c.m16 && c.vec == 2) {
+    l = std::max(l, stage_lds_bytes<LD, LH, LH, 2>());
+    MT_TS_LAUNCH(2, false, MT_F32, MT_F32, MT_BF16);
+  } else if constexpr (S2 == 1) {
+    if (c.m16) {                                     // fp32 sources rounded to bf16 in the staging
+      l = std::max(l, bstage_lds_bytes<LD, LH, LH, 2, 4>());
+      MT_TS_LAUNCH(2, true, MT_F32, MT_F32, MT_BF16);
+    } else {
+      l = std::max(l, stage_lds_bytes<LD, LH, LH, 1>());
+      MT_TS_LAUNCH(1, false, MT_F32, MT_F32, MT_BF16);
+    }
+  }
+#undef MT_TS_LAUNCH16
+#undef MT_TS_LAUNCH
+}
+static int launch_tapsplit(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  ConvKParams P;
+  if (int rc = conv_fill(P, p, conv_tile(c), 27, FCK)) return rc;
+  const dim3 grid = conv_grid(P, 32);
+  if (p->SH != 2) launch_tapsplit_t<1, 1>(c, grid, st, P);
+  else if (p->SD == 2) launch_tapsplit_t<2, 2>(c, grid, st, P);
+  else launch_tapsplit_t<1, 2>(c, grid, st, P);
+  MT_CHECK_LAUNCH("conv3d_tapsplit");
+  return MT_OK;
+}
+
+static int launch_stem(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  ConvKParams P;
+  if (int rc = conv_fill(P, p, conv_tile(c), 27, FCK)) return rc;
+  const dim3 grid = conv_grid(P, 32);
+  if (c.os == MT_F16) hipLaunchKernelGGL((conv_stem_kernel<MT_F16>), grid, dim3(256), 0, st, P);
+  else if (c.os == MT_BF16) hipLaunchKernelGGL((conv_stem_kernel<MT_BF16>), grid, dim3(256), 0, st, P);
+  else hipLaunchKernelGGL((conv_stem_kernel<MT_F32>), grid, dim3(256), 0, st, P);
+  MT_CHECK_LAUNCH("conv3d_stem");
+  return MT_OK;
+}
+
+template <int MW, int RH, int TD, int VEC, int NT, int NW, int KD = 3, int XS = MT_F32, int OS = MT_F32, int MTY = MT_BF16>
+static int launch_bf16_t(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  ConvKParams P;
+  if (int rc = conv_fill(P, p, conv_tile(c), KD * 9, FCK)) return rc;
+  constexpr int TH = (32 / MW) * RH, TW = MW;
+  const size_t ldsb = bstage_lds_bytes<TD + KD - 1, TH + 2, TW + 2, VEC, NW, (BF_SWZ ? BFP_SWZ : BFP)>();
+  dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(mt_cdiv(p->Cout, 32), NT), 1);
+  return conv_launch_lds(conv_bf16_kernel<MW, RH, TD, VEC, NT, NW, KD, XS, OS, MTY>, grid, dim3(64 * NW), ldsb, st, P, "conv3d_bf16");
+}
+static int launch_bf16(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  // NT = 2 (64 output channels per workgroup) measured slower: 0.197 vs 0.179 ms on 64->64 @ 24x96x96; 8 waves: no gain
+  MT_REQUIRE(c.xs == conv_src_dtype(p) && c.xs == p->odtype, "conv3d: conv_bf16_kernel takes ONE storage type on all operands (ask mt_conv3d_io_supported)");
+#define MT_BF_CASE(MW_, RH_, TD_, NW_)                                                       \
+  if (c.g.MW == MW_ && c.g.TD == TD_) {                                                      \
+    if (c.xs == MT_F16) return p->KD == 1 ? launch_bf16_t<MW_, RH_, TD_, 4, 1, NW_, 1, MT_F16, MT_F16, MT_F16>(p, c, st) : launch_bf16_t<MW_, RH_, TD_, 4, 1, NW_, 3, MT_F16, MT_F16, MT_F16>(p, c, st); \
+    if (c.xs == MT_BF16) return p->KD == 1 ? launch_bf16_t<MW_, RH_, TD_, 4, 1, NW_, 1, MT_BF16, MT_BF16, MT_BF16>(p, c, st) : launch_bf16_t<MW_, RH_, TD_, 4, 1, NW_, 3, MT_BF16, MT_BF16, MT_BF16>(p, c, st); \
+    return p->KD == 1 ? launch_bf16_t<MW_, RH_, TD_, 2, 1, NW_, 1>(p, c, st) : launch_bf16_t<MW_, RH_, TD_, 2, 1, NW_>(p, c, st); \
+  }
+  MT_BF_CASE(32, 4, 4, 4)
+  MT_BF_CASE(32, 4, 2, 4)
+  MT_BF_CASE(16, 4, 2, 4)
+#undef MT_BF_CASE
+  mt_set_error("conv3d bf16: bad tile configuration %d x %d x %d", c.g.MW, c.g.RH, c.g.TD);
+  return MT_EINVAL;
+}
+
+static int launch_x16(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  const ConvTile t = conv_tile(c);
+  X16Params P;
+  P.c = *p;
+  if (P.c.nsrc == 1) { P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0; }
+  P.tilesD = mt_cdiv(p->Do, t.D); P.tilesH = mt_cdiv(p->Ho, t.H); P.tilesW = mt_cdiv(p->Wo, t.W);
+  P.nsb = P.tilesD * P.tilesH * P.tilesW;
+  P.ncot = mt_cdiv(p->Cout, 32);
+  P.nitems = p->N * P.nsb * P.ncot;
+  P.nchunks = mt_build_chunks(p->src[0].C, p->nsrc == 2 ? p->src[1].C : 0, FCK, P.chunk);
+  MT_REQUIRE(P.nchunks > 0, "conv3d (x16): too many channel chunks (Cin=%d)", p->Cin);
+  P.npairs = 0;
+  for (int i = 0; i < P.nchunks; ++P.npairs) {
+    const bool two = i + 1 < P.nchunks && P.chunk[i + 1].src == P.chunk[i].src && P.chunk[i + 1].c0 == P.chunk[i].c0 + 16;
+    P.pair[P.npairs][0] = (short)i; P.pair[P.npairs][1] = (short)(two ? i + 1 : -1);
+    i += two ? 2 : 1;
+  }
+  P.nwg = mt_conv_x16_workgroups(P.nitems);
+  if (p->max_workgroups > 0 && P.nwg > p->max_workgroups) P.nwg = p->max_workgroups;
+  return mt_launch_conv_x16(P, p->KD, c.xs, st);
+}
+
+static int launch_wino(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  MT_REQUIRE(p->bstats.y == nullptr || (c.bstats && p->stats_part != nullptr && p->bstats.mean && p->bstats.rstd &&
+                                        p->bstats.c0 >= 0 && p->bstats.C > 0 && p->bstats.c0 + p->bstats.C <= p->Cout),
+             "conv3d: bstats set on a problem this kernel does not compute them for (ask mt_conv3d_bwd_stats_supported)");
+  ConvKParams P;
+  if (int rc = conv_fill(P, p, conv_tile(c), 27, WCK)) return rc;
+  const int devid = mt_current_device();
+  const size_t l8 = (size_t)(2 * W_RAWF + W_VF) * sizeof(float) + 11 * 256 * 4;          // two raw patches + V + the patch-geometry table
+  // one resident workgroup per CU (126 KiB of LDS each): NW workers per output-channel tile walk over the spatial tiles
+  const int T = P.nsb * p->N, nct = mt_cdiv(p->Cout, 32);
+  int nw = mt_device_cus(devid) / nct; if (nw < 1) nw = 1; if (nw > T) nw = T;
+  if (p->max_workgroups > 0 && nw > p->max_workgroups) nw = p->max_workgroups;       // tests: few workers, many tiles each
+  const bool b = c.family == CONV_WINO_B;
+  static std::atomic<uint64_t> attrb{0}, attrp{0};
+  std::atomic<uint64_t>& attr = b ? attrb : attrp;
+  if (mt_device_pending(attr, devid)) {
+    hipError_t e = hipFuncSetAttribute(b ? (const void*)conv_wino8pb_kernel : (const void*)conv_wino8p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l8);
+    if (e != hipSuccess) { mt_set_error("conv3d: cannot raise dynamic LDS to %zu: %s", l8, hipGetErrorString(e)); return MT_EHIP; }
+    mt_mark_device_done(attr, devid);
+  }
+  if (b) hipLaunchKernelGGL(conv_wino8pb_kernel, dim3((unsigned)nw, (unsigned)nct, 1), dim3(512), l8, st, P);
+  else hipLaunchKernelGGL(conv_wino8p_kernel, dim3((unsigned)nw, (unsigned)nct, 1), dim3(512), l8, st, P);
+  MT_CHECK_LAUNCH(b ? "conv3d_wino8pb" : "conv3d_wino8p");
+  return MT_OK;
+}
+
+static int launch_gather(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  ConvKParams P;
+  if (int rc = conv_fill(P, p, {1, 1, 1}, p->KD * p->KH * p->KW, FCK)) return rc;
+  const long V = (long)p->Do * p->Ho * p->Wo;
+  P.tilesD = P.tilesH = P.tilesW = 1; P.nsb = (int)((V + 127) / 128);
+  dim3 grid = conv_grid(P, 32);
+  // (the <2> and <1> instances below are unreachable; they stay until the device code itself is cleaned up)
+  if (c.m16 && c.os == MT_BF16) hipLaunchKernelGGL((conv_gather_kernel<4, MT_BF16, MT_BF16, true>), grid, dim3(256), 0, st, P);
+  else if (c.m16) hipLaunchKernelGGL((conv_gather_kernel<4, MT_BF16, MT_F32, true>), grid, dim3(256), 0, st, P);
+  else if (c.xs == MT_BF16 && c.os == MT_BF16) hipLaunchKernelGGL((conv_gather_kernel<4, MT_BF16, MT_BF16>), grid, dim3(256), 0, st, P);
+  else if (c.xs == MT_BF16) hipLaunchKernelGGL((conv_gather_kernel<4, MT_BF16, MT_F32>), grid, dim3(256), 0, st, P);
+  else if (c.os == MT_BF16) hipLaunchKernelGGL((conv_gather_kernel<4, MT_F32, MT_BF16>), grid, dim3(256), 0, st, P);
+  else if (c.vec == 4 && c.nt2) {
+    grid.y = (unsigned)mt_cdiv(mt_cdiv(p->Cout, 32), 2);
+    hipLaunchKernelGGL((conv_gather_kernel<4, MT_F32, MT_F32, false, 2>), grid, dim3(256), 0, st, P);
+  }
+  else if (c.vec == 4) hipLaunchKernelGGL(conv_gather_kernel<4>, grid, dim3(256), 0, st, P);
+  else if (c.vec == 2) hipLaunchKernelGGL(conv_gather_kernel<2>, grid, dim3(256), 0, st, P);
+  else hipLaunchKernelGGL(conv_gather_kernel<1>, grid, dim3(256), 0, st, P);
+  MT_CHECK_LAUNCH("conv3d_gather");
+  return MT_OK;
+}
+
+static int launch_rt(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  ConvKParams P;
+  if (int rc = conv_fill(P, p, conv_tile(c), p->KD * p->KH * p->KW, FCK)) return rc;
+  const size_t ldsb = rt_lds(c.g, p);
+#define MT_RT_CASE(MW_, RH_, TD_)                                                                                              \
+  if (c.g.MW == MW_) return c.vec == 2 ? conv_launch_lds(conv_rt_kernel<MW_, RH_, TD_, 2>, conv_grid(P, 32), dim3(256), ldsb, st, P, "conv3d_rt") \
+                                       : conv_launch_lds(conv_rt_kernel<MW_, RH_, TD_, 1>, conv_grid(P, 32), dim3(256), ldsb, st, P, "conv3d_rt");
+  MT_RT_CASE(32, 4, 2)
+  MT_RT_CASE(16, 2, 2)
+  MT_RT_CASE(8, 2, 2)
+#undef MT_RT_CASE
+  return MT_EINVAL;
+}
+
+static int launch_generic(const mt_conv3d_t* p, const ConvChoice& c, hipStream_t st) {
+  ConvKParams P;
+  if (int rc = conv_fill(P, p, conv_tile(c), p->KD * p->KH * p->KW, c.g.CK)) return rc;
+  const size_t ldsb = cfg_lds(c.g, p);
+#define MT_G_INST(MW_, RH_, TD_, CK_, FAST_) conv_launch_lds(conv_fwd_kernel<MW_, RH_, TD_, CK_, FAST_>, conv_grid(P, 32), dim3(256), ldsb, st, P, "conv3d_fwd")
+#define MT_G_IS(MW_, TD_, CK_) (c.g.MW == MW_ && c.g.TD == TD_ && c.g.CK == CK_)
+#define MT_G_CASE(MW_, RH_, TD_, CK_) if (MT_G_IS(MW_, TD_, CK_)) return c.fast ? MT_G_INST(MW_, RH_, TD_, CK_, true) : MT_G_INST(MW_, RH_, TD_, CK_, false);
+  MT_G_CASE(32, 4, 2, 16)
+  MT_G_CASE(16, 2, 2, 16)
+  MT_G_CASE(8, 2, 2, 16)
+  MT_G_CASE(32, 4, 2, 8)
+  if (MT_G_IS(16, 2, 8)) return MT_G_INST(16, 2, 2, 8, false);
+  if (MT_G_IS(8, 2, 8)) return MT_G_INST(8, 2, 2, 8, false);
+  MT_G_CASE(32, 4, 4, 16)
+#undef MT_G_CASE
+#undef MT_G_IS
+#undef MT_G_INST
+  return MT_EINVAL;
 }
 
 extern "C" int mt_conv3d_fwd(const mt_conv3d_t* p, mt_stream_t stream) {
   int rc = conv_validate(p);
   if (rc != MT_OK) return rc;
-  const ConvPlan pl = conv_plan(p);
-  const int i = pl.cfg;
-  MT_REQUIRE(i >= 0, "conv3d: no tile configuration fits LDS");
-  MT_REQUIRE(mt_conv3d_io_supported(p), "conv3d: storage types (src %d/%d, out %d) not taken by the kernel that serves this problem "
+  const ConvChoice c = conv_resolve(p);
+  MT_REQUIRE(c.family != CONV_NONE, "conv3d: no tile configuration fits LDS");
+  MT_REQUIRE(conv_io_served(p, c), "conv3d: storage types (src %d/%d, out %d) not taken by the kernel that serves this problem "
              "(ask mt_conv3d_io_supported, convert with mt_cast)", p->src[0].dtype, p->nsrc == 2 ? p->src[1].dtype : -1, p->odtype);
-  MT_REQUIRE(p->bstats.y == nullptr || pl.kind == CONV_WINO, "conv3d: bstats set on a problem whose kernel does not compute them "
+  MT_REQUIRE(p->bstats.y == nullptr || c.family == CONV_WINO_B, "conv3d: bstats set on a problem whose kernel does not compute them "
              "(ask mt_conv3d_bwd_stats_supported)");
-  if (pl.kind == CONV_BF16 && conv_x16_ok(p, i)) return launch_x16(p, (hipStream_t)stream);
-  if (pl.kind == CONV_BF16) return launch_bf16(p, i, (hipStream_t)stream);
-  const ConvCfg& g = kCfgs[i];
-  hipStream_t st = (hipStream_t)stream;
-  const bool fast = conv_is_fast(p);
-  MT_REQUIRE(p->osD <= 0 || pl.kind == CONV_RT, "conv3d: strided output placement needs the runtime-geometry kernel");
+  MT_REQUIRE(p->osD <= 0 || c.family == CONV_RT, "conv3d: strided output placement needs the runtime-geometry kernel");
   MT_REQUIRE(p->osD <= 0 || (p->stats_part == nullptr && p->osH > 0 && p->osW > 0 &&
              (p->Do - 1) * p->osD + p->ooD < p->OD && (p->Ho - 1) * p->osH + p->ooH < p->OH && (p->Wo - 1) * p->osW + p->ooW < p->OW),
              "conv3d: bad strided output placement");
-  if (pl.kind == CONV_FAST_STRIDED) return launch_fast_strided(p, st);
-  if (pl.kind == CONV_TAPSPLIT) return launch_tapsplit(p, st);
-  if (pl.kind == CONV_STEM) return launch_stem(p, st);
-  if (pl.kind == CONV_WINO) return launch_wino(p, st);
-  if (pl.kind == CONV_RT && conv_gather_ok(p)) return launch_gather(p, st);
-  if (pl.kind == CONV_RT) {
-    const int vec = conv_fast_vec(p);
-    switch (i) {
-      case 0: return vec == 2 ? launch_rt<32, 4, 2, 2>(p, g, st) : launch_rt<32, 4, 2, 1>(p, g, st);
-      case 1: return vec == 2 ? launch_rt<16, 2, 2, 2>(p, g, st) : launch_rt<16, 2, 2, 1>(p, g, st);
-      case 2: return vec == 2 ? launch_rt<8, 2, 2, 2>(p, g, st) : launch_rt<8, 2, 2, 1>(p, g, st);
-      default: return MT_EINVAL;
-    }
+  hipStream_t st = (hipStream_t)stream;
+  switch (c.family) {
+    case CONV_STEM: return launch_stem(p, c, st);
+    case CONV_WINO: case CONV_WINO_B: return launch_wino(p, c, st);
+    case CONV_FAST: return launch_fast(p, c, st);
+    case CONV_TAPSPLIT: return launch_tapsplit(p, c, st);
+    case CONV_FAST_STRIDED: return p->SD == 2 ? launch_fast_strided_t<2>(p, c, st) : launch_fast_strided_t<1>(p, c, st);
+    case CONV_BF16: return launch_bf16(p, c, st);
+    case CONV_X16: return launch_x16(p, c, st);
+    case CONV_GATHER: return launch_gather(p, c, st);
+    case CONV_RT: return launch_rt(p, c, st);
+    default: return launch_generic(p, c, st);
   }
-  if (pl.kind == CONV_FAST) {
-    const int vec = conv_fast_vec(p);
-    if (p->KD == 1) {
-      switch (i) {
-        case 0: return vec == 2 ? launch_fast2<32, 4, 2, 2, 1>(p, g, st) : launch_fast2<32, 4, 2, 1, 1>(p, g, st);
-        case 1: return vec == 2 ? launch_fast2<16, 2, 2, 2, 1>(p, g, st) : launch_fast2<16, 2, 2, 1, 1>(p, g, st);
-        default: return vec == 2 ? launch_fast2<8, 2, 2, 2, 1>(p, g, st) : launch_fast2<8, 2, 2, 1, 1>(p, g, st);
-      }
-    }
-    switch (i) {
-      case 0: return vec == 2 ? launch_fast2<32, 4, 2, 2>(p, g, st) : launch_fast2<32, 4, 2, 1>(p, g, st);
-      case 1: return vec == 2 ? launch_fast2<16, 2, 2, 2>(p, g, st) : launch_fast2<16, 2, 2, 1>(p, g, st);
-      case 2: return vec == 2 ? launch_fast2<8, 2, 2, 2>(p, g, st) : launch_fast2<8, 2, 2, 1>(p, g, st);
-      default: break;
-    }
-  }
-  switch (i) {
-    case 0: return fast ? launch_conv<32, 4, 2, 16, true>(p, g, st) : launch_conv<32, 4, 2, 16, false>(p, g, st);
-    case 1: return fast ? launch_conv<16, 2, 2, 16, true>(p, g, st) : launch_conv<16, 2, 2, 16, false>(p, g, st);
-    case 2: return fast ? launch_conv<8, 2, 2, 16, true>(p, g, st) : launch_conv<8, 2, 2, 16, false>(p, g, st);
-    case 3: return fast ? launch_conv<32, 4, 2, 8, true>(p, g, st) : launch_conv<32, 4, 2, 8, false>(p, g, st);
-    case 4: return launch_conv<16, 2, 2, 8, false>(p, g, st);
-    case 5: return launch_conv<8, 2, 2, 8, false>(p, g, st);
-    case 6: return fast ? launch_conv<32, 4, 4, 16, true>(p, g, st) : launch_conv<32, 4, 4, 16, false>(p, g, st);
-  }
-  return MT_EINVAL;
 }
 
 
 // ------------------------------------------------------------------------------------------------
 // mt_conv3d_bwd_data_strided: see include/mtseg.h.  p carries the FORWARD geometry (Di.. = X dims, Do.. = Y dims, K = 3,
 // S in {(2,2,2), (1,2,2)}, P = 1); src[0] = dY (C = Cout of the conv), out0 = dX (Cin channels).
-static bool bwdd_strided_use_bf16(const mt_conv3d_t* p) {          // p = FORWARD geometry, src[0] = dY
-  const int g_bf16_mode = mt_sel3(p, MT_SEL_M16);
-  constexpr int use = 1;
+// The one decision: conv_bwdd_strided_ks_kernel (fp32 on both sides, 8-byte channel pairs, fewer workgroups than CUs in the 2 x 4 x 16
+// tiling; MT_SEL_TAPSPLIT OFF: never, FORCE: wherever the types fit), else conv_bwdd_strided_kernel with 16-bit matrix inputs and the
+// storage pair (dY, dX), or in fp32 with staging width 2 (channel pairs) or 1.
+struct BwddChoice { bool ks, m16; int vec, xs, os; };
+static BwddChoice bwdd_resolve(const mt_conv3d_t* p) {
   const mt_src_t& s0 = p->src[0];
-  return use && g_bf16_mode && p->mma == 1 && p->Cout >= 16 && !((s0.cs & 1) || (s0.C & 1) || (((uintptr_t)s0.ptr) & (mt_is16(s0.dtype) ? 3 : 7)));
+  const bool pairs = !((s0.cs & 1) || (s0.C & 1));
+  BwddChoice c = {};
+  c.m16 = mt_sel3(p, MT_SEL_M16) && p->mma == 1 && p->Cout >= 16 && pairs && !(((uintptr_t)s0.ptr) & (mt_is16(s0.dtype) ? 3 : 7));
+  c.vec = (pairs && !(((uintptr_t)s0.ptr) & 7)) ? 2 : 1;
+  if (c.m16) {
+    const bool yb = s0.dtype == MT_BF16 && p->odtype == MT_BF16;        // dY and dX bf16; else dY read as fp32, dX bf16 or fp32
+    c.vec = yb ? 4 : 2; c.xs = yb ? MT_BF16 : MT_F32; c.os = p->odtype == MT_BF16 ? MT_BF16 : MT_F32;
+    return c;
+  }
+  const int g_tapsplit = mt_sel3(p, MT_SEL_TAPSPLIT);
+  if (g_tapsplit && s0.dtype == MT_F32 && p->odtype == MT_F32 && c.vec == 2) {
+    const long wgs = (long)p->N * mt_cdiv(mt_cdiv(p->Di, p->SD), 2) * mt_cdiv(mt_cdiv(p->Hi, 2), 4) * mt_cdiv(mt_cdiv(p->Wi, 2), 16) * mt_cdiv(p->Cin, 32);
+    c.ks = wgs < 256 || g_tapsplit >= 2;
+  }
+  return c;
 }
-extern "C" int mt_conv3d_bwd_data_strided_pack_layout(const mt_conv3d_t* p) { return (p != nullptr && bwdd_strided_use_bf16(p)) ? 3 : 1; }
-extern "C" int mt_conv3d_bwd_data_strided_io_supported(const mt_conv3d_t* p) {
-  if (p == nullptr || !mt_dtype_ok(p->src[0].dtype) || !mt_dtype_ok(p->odtype)) return 0;
+extern "C" int mt_conv3d_bwd_data_strided_pack_layout(const mt_conv3d_t* p) { return (p != nullptr && bwdd_resolve(p).m16) ? 3 : 1; }
+static int bwdd_io_served(const mt_conv3d_t* p, const BwddChoice& c) {
+  if (!mt_dtype_ok(p->src[0].dtype) || !mt_dtype_ok(p->odtype)) return 0;
   if (p->src[0].dtype == MT_F32 && p->odtype == MT_F32) return 1;
-  if (!bwdd_strided_use_bf16(p) || p->src[0].dtype == MT_F16) return 0;        // gradients are fp32 or bf16
+  if (!c.m16 || p->src[0].dtype == MT_F16) return 0;        // gradients are fp32 or bf16
   // dX bf16 (channel-pair dwords: even Cin / stride, dword-aligned base) from dY bf16 or fp32
   return (p->odtype == MT_BF16 && !(p->Cin & 1) && !(p->ocs0 & 1) && !(((uintptr_t)p->out0) & 3)) ? 1 : 0;
 }
-// conv_bwdd_strided_ks_kernel: fp32 on both sides, 8-byte channel pairs, fewer workgroups than CUs in the 2 x 4 x 16 tiling
-// (option "conv_tapsplit" / MT_CONV_TAPSPLIT = 0: never; 2: wherever the types fit)
-static bool bwdd_strided_use_ks(const mt_conv3d_t* p) {
-  const int g_tapsplit = mt_sel3(p, MT_SEL_TAPSPLIT);
-  const mt_src_t& s0 = p->src[0];
-  if (!g_tapsplit || bwdd_strided_use_bf16(p) || s0.dtype != MT_F32 || p->odtype != MT_F32) return false;
-  if ((s0.cs & 1) || (s0.C & 1) || (((uintptr_t)s0.ptr) & 7)) return false;
-  const long wgs = (long)p->N * mt_cdiv(mt_cdiv(p->Di, p->SD), 2) * mt_cdiv(mt_cdiv(p->Hi, 2), 4) * mt_cdiv(mt_cdiv(p->Wi, 2), 16) * mt_cdiv(p->Cin, 32);
-  return wgs < 256 || g_tapsplit >= 2;
-}
+extern "C" int mt_conv3d_bwd_data_strided_io_supported(const mt_conv3d_t* p) { return p == nullptr ? 0 : bwdd_io_served(p, bwdd_resolve(p)); }
 template <int SD, int SH, int SW>
 static int launch_bwdd_strided(const mt_conv3d_t* p, hipStream_t st) {
   constexpr int TD = 2, TH = 4, TW = 16;
   constexpr int LD = TD + (SD == 2 ? 1 : 2), LH = TH + (SH == 2 ? 1 : 2), LW = TW + (SW == 2 ? 1 : 2);
+  const BwddChoice c = bwdd_resolve(p);
+  MT_REQUIRE(bwdd_io_served(p, c), "bwd_data_strided: storage types not taken by the kernel that serves this problem (ask mt_conv3d_bwd_data_strided_io_supported)");
+  const ConvTile t = c.ks ? ConvTile{TD, 4, 4} : ConvTile{TD, TH, TW};   // ks: one 2 x 4 x 4 tile per workgroup, the chunk's K split over the waves
   ConvKParams P;
-  P.c = *p;
+  if (int rc = conv_fill(P, p, t, 27, FCK)) return rc;
   // the kernel sees a stride-1 problem over the dY grid: input = dY (dims Do,Ho,Wo), channels Cout -> Cin
   P.c.Di = p->Do; P.c.Hi = p->Ho; P.c.Wi = p->Wo;
   P.c.OD = p->Di; P.c.OH = p->Hi; P.c.OW = p->Wi;
   P.c.Cin = p->Cout; P.c.Cout = p->Cin;
-  P.c.nsrc = 1; P.c.src[1] = P.c.src[0]; P.c.src[1].C = 0;
-  const int gD = mt_cdiv(p->Di, SD), gH = mt_cdiv(p->Hi, SH), gW = mt_cdiv(p->Wi, SW);   // dY positions that reach some dX
-  P.tilesD = mt_cdiv(gD, TD); P.tilesH = mt_cdiv(gH, TH); P.tilesW = mt_cdiv(gW, TW);
+  // the tiles cover the dY positions that reach some dX
+  P.tilesD = mt_cdiv(mt_cdiv(p->Di, SD), t.D); P.tilesH = mt_cdiv(mt_cdiv(p->Hi, SH), t.H); P.tilesW = mt_cdiv(mt_cdiv(p->Wi, SW), t.W);
   P.nsb = P.tilesD * P.tilesH * P.tilesW;
-  P.ntaps = 27; P.dbg = 0; P.stagger = 0;
-  P.nchunks = mt_build_chunks(p->Cout, 0, FCK, P.chunk);
-  MT_REQUIRE(P.nchunks > 0, "bwd_data_strided: too many channel chunks (Cout=%d)", p->Cout);
-  dim3 grid((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(p->Cin, 32), 1);
-  const mt_src_t& s0 = p->src[0];
-  const bool v2 = !((s0.cs & 1) || (s0.C & 1) || (((uintptr_t)s0.ptr) & 7));
-  MT_REQUIRE(mt_conv3d_bwd_data_strided_io_supported(p), "bwd_data_strided: storage types not taken by the kernel that serves this problem (ask mt_conv3d_bwd_data_strided_io_supported)");
-  if (bwdd_strided_use_ks(p)) {           // under-filled grid: one 2 x 4 x 4 tile per workgroup, the chunk's K split over the waves
+  const dim3 grid = conv_grid(P, 32);
+  if (c.ks) {
     constexpr int KLD = 2 + (SD == 2 ? 1 : 2), KLH = 4 + 1, KLW = 4 + 1;
-    P.tilesH = mt_cdiv(gH, 4); P.tilesW = mt_cdiv(gW, 4);
-    P.nsb = P.tilesD * P.tilesH * P.tilesW;
     size_t l = stage_lds_bytes<KLD, KLH, KLW, 2>(); if (l < (size_t)4 * 16 * 64 * sizeof(float)) l = (size_t)4 * 16 * 64 * sizeof(float);
-    hipLaunchKernelGGL((conv_bwdd_strided_ks_kernel<SD, SH, SW>), dim3((unsigned)(P.nsb * p->N), (unsigned)mt_cdiv(p->Cin, 32), 1), dim3(256), l, st, P);
+    hipLaunchKernelGGL((conv_bwdd_strided_ks_kernel<SD, SH, SW>), grid, dim3(256), l, st, P);
     MT_CHECK_LAUNCH("conv_bwdd_strided_ks");
     return MT_OK;
   }
-  if (bwdd_strided_use_bf16(p)) {
-    if (s0.dtype == MT_BF16 && p->odtype == MT_BF16)
-      hipLaunchKernelGGL((conv_bwdd_strided_kernel<SD, SH, SW, 4, true, MT_BF16, MT_BF16>), grid, dim3(256), (bstage_lds_bytes<LD, LH, LW, 4, 4>()), st, P);
-    else if (p->odtype == MT_BF16)       // dY of an fp32 level, dX bf16
-      hipLaunchKernelGGL((conv_bwdd_strided_kernel<SD, SH, SW, 2, true, MT_F32, MT_BF16>), grid, dim3(256), (bstage_lds_bytes<LD, LH, LW, 2, 4>()), st, P);
-    else
-      hipLaunchKernelGGL((conv_bwdd_strided_kernel<SD, SH, SW, 2, true>), grid, dim3(256), (bstage_lds_bytes<LD, LH, LW, 2, 4>()), st, P);
-  }
-  else if (v2) hipLaunchKernelGGL((conv_bwdd_strided_kernel<SD, SH, SW, 2>), grid, dim3(256), (stage_lds_bytes<LD, LH, LW, 2>()), st, P);
-  else    hipLaunchKernelGGL((conv_bwdd_strided_kernel<SD, SH, SW, 1>), grid, dim3(256), (stage_lds_bytes<LD, LH, LW, 1>()), st, P);
+  if (c.m16 && c.vec == 4) hipLaunchKernelGGL((conv_bwdd_strided_kernel<SD, SH, SW, 4, true, MT_BF16, MT_BF16>), grid, dim3(256), (bstage_lds_bytes<LD, LH, LW, 4, 4>()), st, P);
+  else if (c.m16 && c.os == MT_BF16) hipLaunchKernelGGL((conv_bwdd_strided_kernel<SD, SH, SW, 2, true, MT_F32, MT_BF16>), grid, dim3(256), (bstage_lds_bytes<LD, LH, LW, 2, 4>()), st, P);
+  else if (c.m16) hipLaunchKernelGGL((conv_bwdd_strided_kernel<SD, SH, SW, 2, true>), grid, dim3(256), (bstage_lds_bytes<LD, LH, LW, 2, 4>()), st, P);
+  else if (c.vec == 2) hipLaunchKernelGGL((conv_bwdd_strided_kernel<SD, SH, SW, 2>), grid, dim3(256), (stage_lds_bytes<LD, LH, LW, 2>()), st, P);
+  else hipLaunchKernelGGL((conv_bwdd_strided_kernel<SD, SH, SW, 1>), grid, dim3(256), (stage_lds_bytes<LD, LH, LW, 1>()), st, P);
   MT_CHECK_LAUNCH("conv_bwdd_strided");
   return MT_OK;
 }
@@ -2716,13 +2618,9 @@ extern "C" int mt_conv3d_bwd_data_strided_supported(const mt_conv3d_t* p) {
 }
 extern "C" int mt_conv3d_bwd_data_strided_kernel_name(const mt_conv3d_t* p, char* buf, size_t n) {
   if (p == nullptr || buf == nullptr || n == 0 || !mt_conv3d_bwd_data_strided_supported(p)) return MT_EINVAL;
-  const mt_src_t& s0 = p->src[0];
-  const bool v2 = !((s0.cs & 1) || (s0.C & 1) || (((uintptr_t)s0.ptr) & 7));
-  if (bwdd_strided_use_ks(p)) { snprintf(buf, n, "conv_bwdd_strided_ks_kernel<%d, 2, 2>", p->SD); return MT_OK; }
-  if (bwdd_strided_use_bf16(p)) {
-    if (s0.dtype == MT_BF16 && p->odtype == MT_BF16) snprintf(buf, n, "conv_bwdd_strided_kernel<%d, 2, 2, 4, true, 1, 1>", p->SD);
-    else snprintf(buf, n, "conv_bwdd_strided_kernel<%d, 2, 2, 2, true, 0, %d>", p->SD, p->odtype == MT_BF16 ? 1 : 0);
-  } else snprintf(buf, n, "conv_bwdd_strided_kernel<%d, 2, 2, %d, false, 0, 0>", p->SD, v2 ? 2 : 1);
+  const BwddChoice c = bwdd_resolve(p);
+  if (c.ks) snprintf(buf, n, "conv_bwdd_strided_ks_kernel<%d, 2, 2>", p->SD);
+  else snprintf(buf, n, "conv_bwdd_strided_kernel<%d, 2, 2, %d, %s, %d, %d>", p->SD, c.vec, c.m16 ? "true" : "false", c.xs, c.os);
   return MT_OK;
 }
 extern "C" int mt_conv3d_bwd_data_strided(const mt_conv3d_t* p, mt_stream_t stream) {

@@ -1,4 +1,4 @@
-"""Shared by tests/test_bwdw_dispatch_cpu.py and tools/record_bwdw_dispatch.py (not a test module).
+"""Shared by tests/test_bwdw_dispatch_cpu.py, tests/conv_dispatch_cases.py and tools/record_dispatch.py (not a test module).
 
 The backward-weight dispatch table: which kernel `mt_conv3d_bwd_weight` takes for a problem, how much workspace the query asks for and
 whether the storage types are served.  `cases()` yields the problems as (mt_conv3d_t, mt_src_t) pairs whose pointers are fake, non-null
@@ -11,6 +11,8 @@ random-number generator.  `EXTRA` adds rows for kernel names a uniform sample of
 """
 import ctypes as C
 import itertools
+
+import numpy as np
 
 MT_F32, MT_BF16, MT_F16 = 0, 1, 2
 SEL_OFF, SEL_FORCE = 1, 2
@@ -69,21 +71,36 @@ def _pick(axes, h):
     return tuple(out)
 
 
+def thinned(major_axes, minor_axes, minor_default, extra):
+    """[(major, minor)]: the full product of the major axes, each row once with the default minor and once with a hash-drawn one."""
+    out = []
+    n_minor = 1
+    for ax in minor_axes:
+        n_minor *= len(ax)
+    for i, major in enumerate(itertools.product(*major_axes)):
+        out.append((major, minor_default))
+        out.append((major, _pick(minor_axes, _mix(i) % n_minor)))
+    out.extend(extra)
+    return out
+
+
+def _first_diff(rows, got, want):
+    bad = np.flatnonzero(np.asarray(got) != np.asarray(want))
+    if bad.size == 0:
+        return None
+    i = int(bad[0])
+    return "%d rows differ; first is row %d %r: got %r, recorded %r" % (bad.size, i, rows[i], got[i], want[i])
+
+
 # (major, minor) rows beyond the thinned product (see the module docstring)
 EXTRA = []
+PREFIX = ''                                                         # of this table's keys in its .npz
+COLUMNS = [('workspace', 'int64'), ('io_supported', 'uint8')]       # what query() returns after the kernel name
 
 
 def rows():
     """[(major, minor)] of the table, in its fixed order."""
-    out = []
-    n_minor = 1
-    for ax in MINOR:
-        n_minor *= len(ax)
-    for i, major in enumerate(itertools.product(*MAJOR)):
-        out.append((major, MINOR_DEFAULT))
-        out.append((major, _pick(MINOR, _mix(i) % n_minor)))
-    out.extend(EXTRA)
-    return out
+    return thinned(MAJOR, MINOR, MINOR_DEFAULT, EXTRA)
 
 
 _BASE = 0x7f0000000000          # fake device addresses, 256-byte aligned, never dereferenced
@@ -144,3 +161,14 @@ def query_all(lib, pairs=None):
         n, w, s = query(lib, p, y)
         names.append(n), ws.append(w), io.append(s)
     return names, ws, io
+
+
+def ask(lib, t):
+    """names and {column: list} over the rows of a table t (this module, or a conv_dispatch_cases.Table): what tools/record_dispatch.py saves."""
+    names, cols = [], {k: [] for k, _ in t.COLUMNS}
+    for major, minor in t.rows():
+        got = t.query(lib, *t.problem(major, minor))
+        names.append(got[0])
+        for (k, _), v in zip(t.COLUMNS, got[1:]):
+            cols[k].append(v)
+    return names, cols

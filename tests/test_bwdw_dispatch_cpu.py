@@ -1,5 +1,5 @@
 """Backward-weight dispatch is pinned row by row (no GPU): for every problem of bwdw_dispatch_cases the kernel name, the workspace
-query and io_supported equal tests/golden/bwdw_dispatch.npz (tools/record_bwdw_dispatch.py).  A change of dispatch policy shows up
+query and io_supported equal tests/golden/bwdw_dispatch.npz (tools/record_dispatch.py --table bwdw).  A change of dispatch policy shows up
 as a re-recorded table."""
 import os
 
@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import bwdw_dispatch_cases as BC
+from bwdw_dispatch_cases import _first_diff
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'bwdw_dispatch.npz')
 
@@ -22,14 +23,6 @@ def table():
     gold = np.load(GOLDEN)
     names, ws, io = BC.query_all(_lib.load())
     return gold, names, ws, io
-
-
-def _first_diff(rows, got, want):
-    bad = np.flatnonzero(np.asarray(got) != np.asarray(want))
-    if bad.size == 0:
-        return None
-    i = int(bad[0])
-    return "%d rows differ; first is row %d %r: got %r, recorded %r" % (bad.size, i, rows[i], got[i], want[i])
 
 
 def test_kernel_names_match_the_recorded_table(table):
