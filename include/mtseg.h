@@ -209,6 +209,8 @@ int mt_conv3d_bwd_stats_supported(const mt_conv3d_t* p); /* 1 when the kernel th
  * (tests assert that full-size problems run on the Winograd / strided / stem kernels; bench.py groups its timings by it) */
 int mt_conv3d_bwd_weight_kernel_name(const mt_conv3d_t* p, const mt_src_t* ysrc, char* buf, size_t n);
 int mt_conv3d_bwd_data_strided_kernel_name(const mt_conv3d_t* p, char* buf, size_t n);
+/* mt_pointwise_kernel_name, mt_pointwise_launch_shape and mt_head_bwd_kernel_name, the same for mt_pointwise_fwd and mt_head_bwd, are
+ * declared below, after mt_pointwise_t. */
 
 /* ---- backward-weight -------------------------------------------------------------------------
  * dW[tap][ci][co] = sum_{n,o} X[n, o*S + t - P, ci] * Y[n, o, co]   (autograd of nn.Conv3d /
@@ -252,6 +254,13 @@ int mt_pointwise_io_supported(const mt_pointwise_t* p);
 /* pack layout (mt_pack_conv_weights, ck = 16) of the weights this problem's launch reads: 1, or 4 (fp16 B fragments) when p->mma == 1
  * and the launch multiplies in fp16 (transposed convolutions and 33..64-channel heads over fp16 activations). */
 int mt_pointwise_pack_layout(const mt_pointwise_t* p);   /* 1 when p->src.dtype / p->odtype are read / written natively (see MT_F16) */
+/* The kernel instance mt_pointwise_fwd(p) launches (profiler name, e.g. "pw_fast_kernel<4, 2, 2, true>": taps per workgroup, source and
+ * destination storage type, fp16 products) and the return code the launch would give, without launching: a problem the launch refuses is
+ * refused here with the same code.  mt_pointwise_launch_shape adds what a template name does not show: grid x, y, z and the store form
+ * of the transposed convolutions (0 dword stores, 1 16-byte pieces per voxel, 2 one linear run per tap pair); eight taps without
+ * statistics run as <4, ...> with z = 2.  Neither touches a device. */
+int mt_pointwise_kernel_name(const mt_pointwise_t* p, char* buf, size_t n);
+int mt_pointwise_launch_shape(const mt_pointwise_t* p, int32_t shape[4]);
 /* Backward of a 1x1x1 segmentation head (generic_UNet.py:349-351, generic_modular_UNet.py:244,251: seg_outputs / deep_supervision_outputs)
  * in ONE pass over (x, dY):  dX[n,v,ci] (+)= sum_co dY[n,v,co] W[co,ci] (gradient w.r.t. the lazily ACTIVATED head input),
  * dW[co*s_co + ci*s_ci] (+)= sum_{n,v} act(x)[n,v,ci] dY[n,v,co], dbias[co] (+)= sum dY.  Cin, Cout <= 64; mt_head_bwd_supported says
@@ -266,6 +275,10 @@ int mt_head_bwd(const mt_src_t* x, const float* dy, int dycs, int N, long V, int
                 float* dx, int dxcs, int dxdtype /* storage type of dx: fp32, or bf16 with a 16-bit x */, int accumulate_dx, float* dw,
                 long s_ci, long s_co, float* dbias, int accumulate_dw, int* dbias_done, void* ws, size_t ws_bytes, mt_stream_t stream);
 int mt_head_bwd_io_supported(int xdtype, int xcs, int dxdtype, int dxcs, int Cin, int Cout);
+/* the main kernel instance mt_head_bwd launches for these operands and, in *dbias_done (may be NULL), what the launch would report;
+ * returns the launch's code for what it can see (no dy / dx / dw / workspace here).  Touches no device. */
+int mt_head_bwd_kernel_name(const mt_src_t* x, int dycs, int N, long V, int Cin, int Cout, int dxcs, int dxdtype, char* buf, size_t n,
+                            int* dbias_done);
 
 
 /* ---- InstanceNorm3d(eps, affine) + LeakyReLU (generic_UNet.py:63-64,69-70) ------------------- */

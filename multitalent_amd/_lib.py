@@ -102,6 +102,9 @@ SIGNATURES = {
     'mt_head_bwd_io_supported': (_i, [_i, _i, _i, _i, _i, _i]),
     'mt_pointwise_io_supported': (_i, [_P(mt_pointwise_t)]),
     'mt_pointwise_pack_layout': (_i, [_P(mt_pointwise_t)]),
+    'mt_pointwise_kernel_name': (_i, [_P(mt_pointwise_t), C.c_char_p, _sz]),
+    'mt_pointwise_launch_shape': (_i, [_P(mt_pointwise_t), _P(C.c_int32)]),
+    'mt_head_bwd_kernel_name': (_i, [_P(mt_src_t), _i, _i, _l, _i, _i, _i, _i, C.c_char_p, _sz, _P(C.c_int)]),
     'mt_inorm_finalize': (_i, [_vp, _i, _i, _i, _d, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     'mt_inorm_lrelu_apply': (_i, [_vp, _i, _vp, _vp, _f, _vp, _i, _vp, _vp, _f, _vp, _i, _i, _l, _i, _i, _vp]),
     'mt_inorm_bwd_workspace': (_sz, [_i, _l, _i]),

@@ -2886,8 +2886,7 @@ static int pack_fill(PackParams& P, size_t* packed_floats, const float* w, float
   P.has_tm = tapmap != nullptr;
   for (int d = 0; d < 3; ++d) { P.tb[d] = tapmap ? tapmap[2 * d] : 0; P.ts[d] = tapmap ? tapmap[2 * d + 1] : 1; }
   P.s_ci = s_ci; P.s_co = s_co; P.s_kd = s_kd; P.s_kh = s_kh; P.s_kw = s_kw;
-  constexpr int tiled = 1;
-  P.contig = (tiled && tapmap == nullptr && ck <= 16 && KD * KH * KW <= 27 && s_kw == 1 && s_kh == KW && s_kd == (long)KH * KW && s_ci == (long)KD * KH * KW) ? 1 : 0;
+  P.contig = (tapmap == nullptr && ck <= 16 && KD * KH * KW <= 27 && s_kw == 1 && s_kh == KW && s_kd == (long)KH * KW && s_ci == (long)KD * KH * KW) ? 1 : 0;
   return MT_OK;
 }
 extern "C" size_t mt_pack_desc_size(void) { return sizeof(PackParams); }

@@ -514,9 +514,8 @@ extern "C" int mt_inorm_lrelu_bwd(float* g, int gcs, const float* y, int ycs, co
   // contiguous tensors take the vectorised lane-constant-channel path
   const int vec = (gcs == C && ycs == C && ag_fast(ydtype, gdtype)) ? dense_vec(C, V * C, gdtype, {g, y}) : 0;
   const bool contig = vec > 0 && (C / vec <= 256);
-  constexpr int small_on = 1;
   const int svec = gdtype == MT_F32 ? 4 : 8;
-  if (small_on && contig && part == nullptr && vec == svec && (long)N * V <= INORM_SMALL_MAX) {
+  if (contig && part == nullptr && vec == svec && (long)N * V <= INORM_SMALL_MAX) {
     InBwdSmall S;
     S.g = g; S.y = y; S.mean = mean; S.rstd = rstd; S.gamma = gamma; S.beta = beta; S.slope = slope; S.V = V; S.C = C; S.N = N;
     S.dgamma = dgamma; S.dbeta = dbeta; S.dbias = dbias;

@@ -422,6 +422,19 @@ def pointwise_pack_layout(p):
     return _lib.load().mt_pointwise_pack_layout(C.byref(p))
 
 
+def pointwise_kernel_name(p):
+    buf = C.create_string_buffer(128)
+    _lib.check(_lib.load().mt_pointwise_kernel_name(C.byref(p), buf, 128), 'pointwise_kernel_name')
+    return buf.value.decode()
+
+
+def pointwise_launch_shape(p):
+    """(grid x, y, z, store form `wide` 0 / 1 / 2) of the launch mt_pointwise_fwd makes for p."""
+    shape = (C.c_int32 * 4)()
+    _lib.check(_lib.load().mt_pointwise_launch_shape(C.byref(p), shape), 'pointwise_launch_shape')
+    return tuple(shape)
+
+
 def pointwise_fwd(p):
     _lib.check(_lib.load().mt_pointwise_fwd(C.byref(p), _stream()), 'pointwise_fwd')
 
@@ -441,6 +454,15 @@ def head_bwd(x, dy, wpack_bwd, dx, accumulate_dx, dw, s_ci, s_co, dbias, accumul
                                C.c_void_p(dx.data_ptr()), dx.cs, dx.dt, int(accumulate_dx), _ptr(dw), int(s_ci), int(s_co), _ptr(dbias),
                                int(accumulate_dw), C.byref(done), _ptr(ws), ws.numel() * ws.element_size(), _stream()), 'head_bwd')
     return bool(done.value)
+
+
+def head_bwd_kernel_name(x, dy, dx):
+    """(main kernel instance, dbias_done) of the launch head_bwd makes for these operands."""
+    xs = x.src()
+    buf, done = C.create_string_buffer(128), C.c_int(0)
+    _lib.check(_lib.load().mt_head_bwd_kernel_name(C.byref(xs), dy.cs, x.N, x.V, x.C, dy.C, dx.cs, dx.dt, buf, 128, C.byref(done)),
+               'head_bwd_kernel_name')
+    return buf.value.decode(), bool(done.value)
 
 
 def head_bwd_io_supported(x, dx, Cout):

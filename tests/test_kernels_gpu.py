@@ -580,6 +580,7 @@ def test_conv_bwd_weight_bf16_1x3x3(dev, Cin, Cout, shape):
     (24, 32, (2, 2, 32), (2, 2, 2), 0),
     (60, 30, (3, 4, 32), (2, 2, 2), 0),      # dense output (the engine's transposed convs): one linear run per (kd, kh) pair
     (20, 14, (2, 3, 64), (1, 2, 2), 0),
+    (20, 14, (2, 3, 5), (1, 1, 2), 0),       # two taps: pw_fast_kernel<2, ...>
 ])
 def test_pointwise_tconv_and_heads(dev, Cin, Cout, base, so, extra):
     ops = _ops()
@@ -607,6 +608,77 @@ def test_pointwise_tconv_and_heads(dev, Cin, Cout, base, so, extra):
     got = to_ncdhw(out[..., :Cout].cpu())
     assert relerr(got, ref) < 1e-5
     assert torch.isnan(out[..., Cout:]).all()
+
+
+def test_pointwise_eight_taps_with_statistics(dev):
+    """pw_fast_kernel<8, ...>: a (2,2,2) transposed convolution that also writes statistics partials keeps all eight taps in one
+    workgroup (without them it runs as two workgroups of four) vs F.conv_transpose3d, the partials vs the output's own sums."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(5)
+    N, Cin, Cout, base, so = 2, 20, 14, (2, 3, 5), (2, 2, 2)
+    x = torch.randn((N, Cin) + base, generator=g)
+    w = torch.randn((Cin, Cout) + so, generator=g) / np.sqrt(Cin)
+    ref = F.conv_transpose3d(x, w, stride=so)
+    wd = w.to(dev).contiguous()
+    wp = ops.pack_conv_weights(wd, Cin, 0, Cout, so, ops.conv_weight_strides(wd, transposed_layout=True), False, ops.POINTWISE_CK)
+    out = torch.full((N,) + tuple(b * s for b, s in zip(base, so)) + (Cout,), float('nan'), device=dev)
+    xa = ops.Act(to_ndhwc(x).to(dev))
+    p = ops.fill_pointwise(xa, base, base, (1, 1, 1), so, Cout, wp, None, ops.Act(out))
+    assert ops.pointwise_kernel_name(p) == 'pw_fast_kernel<4, 0, 0, false>' and ops.pointwise_launch_shape(p)[2] == 2
+    part = torch.zeros((N, ops.pointwise_stats_blocks(p), Cout, 2), device=dev)
+    p.stats_part = part.data_ptr()
+    assert ops.pointwise_kernel_name(p) == 'pw_fast_kernel<8, 0, 0, false>' and ops.pointwise_launch_shape(p)[2] == 1
+    ops.pointwise_fwd(p)
+    torch.cuda.synchronize()
+    assert relerr(to_ncdhw(out.cpu()), ref) < 1e-5
+    o = out.double()
+    sm = part.double().sum(1)
+    assert torch.allclose(sm[..., 0], o.sum((1, 2, 3)), rtol=1e-4, atol=1e-3 * o[0, ..., 0].numel() ** 0.5)
+    assert torch.allclose(sm[..., 1], (o * o).sum((1, 2, 3)), rtol=1e-4)
+
+
+@pytest.mark.parametrize("nonlin", [1, 2])
+def test_fused_inference_heads_dword_source(dev, nonlin):
+    """head_flip_accumulate_kernel<1> / head_mirror_accumulate_kernel<1>: an fp32 source sliced at an odd channel offset (odd channel
+    stride, base 4 mod 8) is read dword by dword; both fused heads vs nonlin(F.conv3d) of the activated input, un-flipped."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(16)
+    N, Cin, Cout, shape = 2, 30, 47, (3, 5, 7)
+    x = torch.randn((N, Cin) + shape, generator=g)
+    lz = [(torch.rand((N, Cin), generator=g) + 0.5, torch.randn((N, Cin), generator=g), 0.01)]
+    w = torch.randn((Cout, Cin, 1, 1, 1), generator=g) / np.sqrt(Cin)
+    b = torch.randn(Cout, generator=g)
+    logits = F.conv3d(ref_inputs([x], lz).double(), w.double(), b.double())
+    pred = torch.sigmoid(logits) if nonlin == 1 else torch.softmax(logits, 1)
+    xb = torch.full((N,) + shape + (Cin + 3,), float('nan'), device=dev)
+    xb[..., 1:1 + Cin] = to_ndhwc(x).to(dev)
+    xa = ops.Act(xb, c0=1, C=Cin, scale=lz[0][0].to(dev).contiguous(), shift=lz[0][1].to(dev).contiguous(), slope=0.01)
+    assert xa.src().cs % 2 == 1 and xa.data_ptr() % 8 == 4
+    wd = w.to(dev).contiguous()
+    wp = ops.pack_conv_weights(wd, Cin, 0, Cout, (1, 1, 1), ops.conv_weight_strides(wd), False, ops.POINTWISE_CK)
+    unused = torch.empty((N,) + shape + (Cout,), device=dev)
+    bd = b.to(dev)
+    p = ops.fill_pointwise(xa, shape, shape, (1, 1, 1), (1, 1, 1), Cout, wp, bd, ops.Act(unused))
+    flips = [(True, False, True), (False, True, False)]
+    dims = [[2 + i for i, f in enumerate(fl) if f] for fl in flips]
+    acc = torch.full((Cout,) + shape, float('nan'), device=dev)
+    ops.head_flip_accumulate(p, 0, flips[0], nonlin, 0.5, acc, True)
+    ops.head_flip_accumulate(p, 1, flips[1], nonlin, 0.25, acc, False)
+    big, origin = (5, 8, 9), (1, 2, 2)
+    agg = torch.zeros((Cout,) + big, device=dev)
+    nb = torch.zeros(big, device=dev)
+    gs = torch.rand(shape, generator=g)
+    ops.head_mirror_accumulate(p, 0, flips, nonlin, 0.5, gs.to(dev), agg, nb, big, origin)
+    torch.cuda.synchronize()
+    un = [torch.flip(pred[k], [d - 1 for d in dims[k]]) for k in range(N)]
+    assert relerr(acc.cpu(), 0.5 * un[0] + 0.25 * un[1]) < 1e-5
+    want = torch.zeros((Cout,) + big, dtype=torch.float64)
+    sl = tuple(slice(o, o + s) for o, s in zip(origin, shape))
+    want[(slice(None),) + sl] = gs.double() * 0.5 * (un[0] + un[1])
+    assert relerr(agg.cpu(), want) < 1e-5
+    wnb = torch.zeros(big, dtype=torch.float64)
+    wnb[sl] = gs.double()
+    assert torch.equal(nb.cpu().double(), wnb)
 
 
 def test_instance_norm_fwd_bwd(dev):

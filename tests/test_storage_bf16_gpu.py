@@ -621,6 +621,7 @@ def _pointwise(dev, x, lazy, w_pack_args, base, in_spatial, si, so, Cout, bias, 
     (64, 32, (4, 8, 32), (2, 2, 2), 2),       # concat slot, wide epilogue with 8-byte pieces
     (120, 60, (3, 5, 9), (2, 2, 2), 1),       # ragged: plain epilogue, two output-channel tiles
     (60, 30, (5, 6, 16), (1, 2, 2), 1),
+    (20, 14, (2, 3, 5), (1, 1, 2), 1),        # two taps
 ])
 def test_transposed_conv_fp16_storage_bitexact(dev, Cin, Cout, base, k, ocs_mult):
     ops = _ops()
@@ -654,6 +655,7 @@ def test_heads_read_fp16_activations(dev, Cin, Cout):
 @pytest.mark.parametrize("Cin,Cout,base,k,ocs_mult", [
     (60, 30, (4, 8, 32), (2, 2, 2), 1), (60, 30, (4, 8, 32), (2, 2, 2), 2), (64, 32, (4, 8, 32), (2, 2, 2), 2), (120, 60, (3, 5, 9), (2, 2, 2), 1),
     (60, 30, (5, 6, 16), (1, 2, 2), 1),
+    (20, 14, (2, 3, 5), (1, 1, 2), 1),        # two taps: the M16 form of pw_fast_kernel<2, ...>
 ])
 def test_transposed_conv_fp16_products(dev, Cin, Cout, base, k, ocs_mult):
     """mt_pointwise_t.mma = 1 (ABI v3): the forward transposed conv over fp16 activations multiplies in fp16 (pack layout 4) — against the host

@@ -1,12 +1,15 @@
 #!/usr/bin/env python
-"""Record a dispatch table: the golden file behind tests/test_bwdw_dispatch_cpu.py or tests/test_conv_dispatch_cpu.py.
+"""Record a dispatch table: the golden file behind tests/test_bwdw_dispatch_cpu.py, test_conv_dispatch_cpu.py or test_pw_dispatch_cpu.py.
 
-    python tools/record_dispatch.py --table bwdw|conv [--lib path/to/libmtseg_hip.so] [--out file.npz] [--census N]
+    python tools/record_dispatch.py --table bwdw|conv|pw [--lib path/to/libmtseg_hip.so] [--out file.npz] [--census N]
 
 bwdw: tests/bwdw_dispatch_cases.py -> tests/golden/bwdw_dispatch.npz (mt_conv3d_bwd_weight: kernel name, workspace, io_supported).
 conv: tests/conv_dispatch_cases.py -> tests/golden/conv_dispatch.npz, two sets of rows: FWD (mt_conv3d_fwd: kernel name, ck, pack layout,
 statistics partials, io_supported, bwd_stats_supported) and BWDD (mt_conv3d_bwd_data_strided: kernel name, supported, pack layout,
-io_supported; keys prefixed 'bwdd_').  Kernel names are stored as indices into a name list.
+io_supported; keys prefixed 'bwdd_').
+pw: tests/pw_dispatch_cases.py -> tests/golden/pw_dispatch.npz, two sets of rows: FWD (mt_pointwise_fwd: return code, kernel instance, grid
+and store form, pack layout, io_supported, statistics partials) and HB (mt_head_bwd: return code, kernel instance, dbias_done, supported,
+io_supported, workspace; keys prefixed 'hb_').  Kernel names are stored as indices into a name list.
 
 The queries read descriptors only, so this runs without a GPU; the tables are for 256 compute units (the library's answer without a
 device, and the MI355X's count).  Re-record only when the dispatch POLICY changes on purpose: the diff of the table is then the review
@@ -28,9 +31,11 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 import bwdw_dispatch_cases as BC  # noqa: E402
 import conv_dispatch_cases as CC  # noqa: E402
+import pw_dispatch_cases as PC  # noqa: E402
 from multitalent_amd import _lib  # noqa: E402
 
-TABLES = {'bwdw': ('bwdw_dispatch.npz', [BC]), 'conv': ('conv_dispatch.npz', [CC.FWD, CC.BWDD])}
+TABLES = {'bwdw': ('bwdw_dispatch.npz', [BC]), 'conv': ('conv_dispatch.npz', [CC.FWD, CC.BWDD]),
+          'pw': ('pw_dispatch.npz', [PC.FWD, PC.HB])}
 
 
 def census(lib, t, n, have):
