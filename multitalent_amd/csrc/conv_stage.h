@@ -216,7 +216,7 @@ __device__ __forceinline__ void stage2_store(const Stage2Regs<LD, LH, LW, VEC>& 
             else x[e] = g.v[r][i][e];
             if (has_aff) {
               const float t = fmaf(x[e], sc[e], sh[e]);
-              const float a = fmaxf(t, t * slope);
+              const float a = mt_lrelu(t, slope);          // any slope: the backward-weight dispatch does not restrict it
               x[e] = g.nosel ? a : ((ok && cval[e]) ? a : 0.f);
             } else if (VEC == 2 && e == 1) x[e] = cval[e] ? x[e] : 0.f;
           }

@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const HeadBwdParams P) {
         } else if constexpr (XS == MT_F32) raw = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, o, 0, 0));
         else raw = mt_from16<XS>(__builtin_amdgcn_raw_buffer_load_b16(rx, o, 0, 0));
         const float tt = fmaf(raw, xsc[t], xsh[t]);
-        av[t] = in ? fmaxf(tt, tt * slope) : 0.f;
+        av[t] = in ? (tt > 0.f ? tt : tt * slope) : 0.f;          // (not max(t, slope t): any slope, as mt_src_t defines it)
         if (ones_free && t == NCI - 1 && li == 31) av[t] = in ? 1.f : 0.f;
       }
 #pragma unroll

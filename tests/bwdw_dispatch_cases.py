@@ -84,6 +84,17 @@ def thinned(major_axes, minor_axes, minor_default, extra):
     return out
 
 
+def census_rows(t, n):
+    """n (major, minor) rows drawn by the fixed hash from the FULL product of the axes of a table t (tools/record_dispatch.py --census)."""
+    axes = t.MAJOR + t.MINOR
+    total = 1
+    for ax in axes:
+        total *= len(ax)
+    for i in range(n):
+        pick = _pick(axes, (_mix(i) * 0x100000000 + _mix(i + 0x9e3779b9)) % total)
+        yield pick[:len(t.MAJOR)], pick[len(t.MAJOR):]
+
+
 def _first_diff(rows, got, want):
     bad = np.flatnonzero(np.asarray(got) != np.asarray(want))
     if bad.size == 0:

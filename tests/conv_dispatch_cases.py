@@ -79,6 +79,10 @@ FWD_EXTRA = [
     ((_G333, ((16,), 64), (2, 9, 20), 1, 0, 0, 1), (None, 'ok', 'base2', 8, 3, True, False, True)),    # conv_bf16_kernel<32, 4, 2, 2, 1, 4, 3, 0, 0, 1>
     ((_G133, ((30,), 30), (2, 9, 20), 2, 1, 2, 1), (0.01, 'base4', 'odd_cs', 8, 3, False, True, False)),    # conv_bf16_kernel<32, 4, 2, 4, 1, 4, 1, 1, 1, 1>
     ((_G333, ((16,), 64), (2, 9, 20), 2, 1, 1, 1), (None, 'base4', 'base2', 8, 0, True, True, True)),    # conv_bf16_kernel<32, 4, 2, 4, 1, 4, 3, 1, 1, 1>
+    # the 2 x 4 x 16 tile of conv_fast_kernel with staging width 1 and 2: eight (or one) input channels on a grid too small for the wide tile
+    ((((1, 3, 3), (1, 1, 1), (0, 1, 1), 1, False), ((8,), 8), (2, 4, 16), 1, 0, 0, 1), (None, 'base4', 'odd_cs', 40, 3, False, False, True)),    # conv_fast_kernel<16, 2, 2, 1, 1>
+    ((((3, 3, 3), (1, 1, 1), (1, 1, 1), 1, False), ((1,), 30), (2, 4, 16), 1, 0, 0, 0), (0.01, 'ok', 'ok', 66, 0, True, True, True)),    # conv_fast_kernel<16, 2, 2, 1, 3>
+    ((((1, 3, 3), (1, 1, 1), (0, 1, 1), 1, False), ((8,), 8), (2, 4, 16), 1, 0, 0, 1), (0.01, 'ok', 'ok', 66, 3, False, True, True)),    # conv_fast_kernel<16, 2, 2, 2, 1>
 ]
 
 

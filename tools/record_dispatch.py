@@ -39,14 +39,11 @@ TABLES = {'bwdw': ('bwdw_dispatch.npz', [BC]), 'conv': ('conv_dispatch.npz', [CC
 
 
 def census(lib, t, n, have):
-    axes = t.MAJOR + t.MINOR
     total = 1
-    for ax in axes:
+    for ax in t.MAJOR + t.MINOR:
         total *= len(ax)
     missing = {}
-    for i in range(n):
-        pick = BC._pick(axes, (BC._mix(i) * 0x100000000 + BC._mix(i + 0x9e3779b9)) % total)
-        major, minor = pick[:len(t.MAJOR)], pick[len(t.MAJOR):]
+    for major, minor in BC.census_rows(t, n):
         name = t.query(lib, *t.problem(major, minor))[0]
         if name not in have:
             missing.setdefault(name, (major, minor))
