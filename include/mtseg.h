@@ -422,6 +422,25 @@ int mt_affine_sample(const float* src, int N, int C, int D, int H, int W, float*
                      const float* mats, int mode, float cval,
                      int planar /* 1: nnU-Net's "dummy 2D" augmentation — every D slice is an independent 2D image, OD == D */,
                      mt_stream_t stream);
+/* Elastic deformation of the same transform (augment_spatial with do_elastic_deform; batchgenerators'
+ * elastic_deform_coordinates): per mesh axis, offsets = gaussian_filter(uniform(-1, 1), sigma, mode='constant', cval=0) * alpha are
+ * added to the zero-centred output mesh before rotation and scaling:  x = M (g(o) + alpha f(o)) + centre.
+ * mt_gaussian_blur_axis_zero: ONE axis pass (0 D, 1 H, 2 W) of scipy.ndimage.gaussian_filter(mode='constant', cval=0, truncate=4)
+ * over src[NC, D, H, W]: w[k] ~ exp(-k^2 / 2 sigma^2), k = -r..r, r = int(4 sigma + 0.5), weights and accumulation in double, taps
+ * off the axis contribute 0 (no reflection), the result is rounded to float32.  sigma: HOST array of NC values, one per (sample,
+ * channel); sigma <= 0 copies that channel.  A sigma whose radius exceeds 64 (sigma >= 16.125) or is NaN is refused with MT_EINVAL
+ * before anything is launched — it is never clamped.  src != dst.
+ * mt_warp_sample: mt_affine_sample with the displaced coordinate above.  field: [N, 3, OD, OH, OW] float32 (components d, h, w),
+ * the element of an output voxel at that voxel's own index; planar: [N, 2, OH, OW] (components h, w), one field shared by all
+ * slices, xd = od.  alpha: [N] device floats; for alpha[n] == 0 sample n's field is not read (it may be uninitialised) and the
+ * result equals mt_affine_sample's bit for bit.  The displaced coordinate may lie anywhere or be non-finite: it is range-checked
+ * in double before any integer conversion, and a NaN gives cval (mode 11: 0) like any coordinate outside the volume. */
+int mt_gaussian_blur_axis_zero(const float* src, float* dst, int NC, int D, int H, int W, int axis,
+                               const float* sigma /* [NC], host */, mt_stream_t stream);
+int mt_warp_sample(const float* src, int N, int C, int D, int H, int W, float* dst, int OD, int OH, int OW,
+                   const float* mats /* N x 12, as mt_affine_sample */,
+                   const float* field /* [N, 3, OD, OH, OW]; planar: [N, 2, OH, OW] */,
+                   const float* alpha /* [N] */, int mode /* 0, 1, 3, 11 */, float cval, int planar, mt_stream_t stream);
 /* Export post-processing: save_segmentation_nifti_from_softmax (segmentation_export.py:27-160) without the
  * resampled 47-channel intermediate — probabilities [C, D, H, W] are interpolated at the OD x OH x OW grid of the original
  * spacing (order 1, skimage/scipy half-pixel rule, edge clamp; sep_axis in 0..2 = the anisotropic axis sampled nearest as in

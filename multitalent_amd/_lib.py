@@ -132,6 +132,8 @@ SIGNATURES = {
     'mt_flip_accumulate': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
     'mt_spline_prefilter3': (_i, [_vp, _i, _i, _i, _i, _i, _vp]),
     'mt_affine_sample': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _f, _i, _vp]),
+    'mt_gaussian_blur_axis_zero': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _P(_f), _vp]),
+    'mt_warp_sample': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp]),
     'mt_resample_classify': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _l, _l, _l, _i, _i, _i, _vp]),
     'mt_ensemble_classify': (_i, [_P(_vp), _i, _i, _i, _i, _i, _l, _vp, _i, _vp, _l, _l, _l, _i, _i, _i, _vp, _l, _vp]),
     'mt_cc_label3d': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -183,9 +183,31 @@ class GammaDevice:
         return data
 
 
+class MaskTransformDevice:
+    """batchgenerators MaskTransform(dct_for_where_it_was_used, mask_idx_in_seg=0, set_outside_to=0)
+    (data_augmentation_moreDA.py:113-115): every channel c with dct[c] true is set to `set_outside_to` where
+    seg[b, mask_idx_in_seg] < 0, i.e. outside the non-zero mask the preprocessing normalised in (use_mask_for_norm).  Elementwise
+    torch glue on whatever device the tensors live on; in place like the reference."""
+
+    def __init__(self, dct_for_where_it_was_used, mask_idx_in_seg=0, set_outside_to=0):
+        self.dct, self.seg_idx, self.outside = dict(dct_for_where_it_was_used), mask_idx_in_seg, set_outside_to
+
+    def __call__(self, data, seg):
+        channels = [int(c) for c, used in self.dct.items() if used]
+        if not channels:
+            return data
+        if seg is None:
+            raise ValueError("MaskTransform needs the segmentation: its label -1 marks the outside of the non-zero mask")
+        outside = seg[:, self.seg_idx] < 0
+        for c in channels:
+            data[:, c].masked_fill_(outside, self.outside)
+        return data
+
+
 class MoreDADeviceAugmenter:
-    """DataLoader3D batches (loader patch = basic_generator_patch_size) -> device -> SpatialTransform -> noise, blur, brightness,
-    contrast, simulated low resolution, gamma (inverted), gamma -> mirror -> {'data', 'target' (one label map; the trainers build
+    """DataLoader3D batches (loader patch = basic_generator_patch_size) -> device -> SpatialTransform (with elastic deformation
+    when params["do_elastic"]) -> noise, blur, brightness, contrast, simulated low resolution, gamma (inverted), gamma -> mirror ->
+    MaskTransform (when params carries "mask_was_used_for_normalization") -> {'data', 'target' (one label map; the trainers build
     the pyramid and remove label -1 on the device), 'properties', 'keys'}: get_moreDA_augmentation's order
     (data_augmentation_moreDA.py:41-153) without the cascade transforms and the CPU worker pool."""
 
@@ -199,7 +221,8 @@ class MoreDADeviceAugmenter:
             scale=params.get("scale_range"), border_mode_data=params.get("border_mode_data"), border_cval_data=0, order_data=order_data,
             border_mode_seg="constant", border_cval_seg=border_val_seg, order_seg=order_seg, random_crop=params.get("random_crop"),
             p_el_per_sample=params.get("p_eldef"), p_scale_per_sample=params.get("p_scale"), p_rot_per_sample=params.get("p_rot"),
-            independent_scale_for_each_axis=params.get("independent_scale_factor_for_each_axis"), dummy_2d=bool(params.get("dummy_2D")))
+            independent_scale_for_each_axis=params.get("independent_scale_factor_for_each_axis"), dummy_2d=bool(params.get("dummy_2D")),
+            alpha=params.get("elastic_deform_alpha"), sigma=params.get("elastic_deform_sigma"))
         ignore_axes = (0,) if params.get("dummy_2D") else None               # data_augmentation_moreDA.py:55-64
         self.color = [GaussianNoiseDevice(p_per_sample=0.1),
                       GaussianBlurDevice((0.5, 1.), different_sigma_per_channel=True, p_per_sample=0.2, p_per_channel=0.5),
@@ -210,6 +233,8 @@ class MoreDADeviceAugmenter:
         if params.get("do_gamma"):
             self.color.append(GammaDevice(params.get("gamma_range"), False, True, params.get("gamma_retain_stats"), params["p_gamma"]))
         self.mirror = MirrorTransformDevice(params.get("mirror_axes")) if params.get("do_mirror") else None
+        used = params.get("mask_was_used_for_normalization")
+        self.mask = MaskTransformDevice(used, mask_idx_in_seg=0, set_outside_to=0) if used is not None else None
 
     def __iter__(self):
         return self
@@ -226,14 +251,17 @@ class MoreDADeviceAugmenter:
             data = t(data)
         if self.mirror is not None:
             data, seg = self.mirror(data, seg)
+        if self.mask is not None:
+            data = self.mask(data, seg)
         return {'data': data, 'target': seg, 'properties': b['properties'], 'keys': b['keys']}
 
 
 def default_3d_augmentation_params():
     """default_3D_augmentation_params (default_data_augmentation.py:39-92) with nnUNetTrainerV2.setup_DA_params's overrides
-    (nnUNetTrainerV2.py:352-389): rotations +-30 degrees, scale (0.7, 1.4), no elastic deformation."""
+    (nnUNetTrainerV2.py:352-389): rotations +-30 degrees, scale (0.7, 1.4), no elastic deformation (its alpha / sigma ranges are
+    the reference's 3D defaults for a trainer that turns it on)."""
     r = 30. / 360 * 2. * np.pi
-    return {"do_elastic": False, "p_eldef": 0.2, "do_scaling": True, "scale_range": (0.7, 1.4),
+    return {"do_elastic": False, "elastic_deform_alpha": (0., 900.), "elastic_deform_sigma": (9., 13.), "p_eldef": 0.2, "do_scaling": True, "scale_range": (0.7, 1.4),
             "independent_scale_factor_for_each_axis": False, "p_scale": 0.2, "do_rotation": True, "rotation_x": (-r, r),
             "rotation_y": (-r, r), "rotation_z": (-r, r), "rotation_p_per_axis": 1, "p_rot": 0.2, "random_crop": False,
             "do_gamma": True, "gamma_retain_stats": True, "gamma_range": (0.7, 1.5), "p_gamma": 0.3, "do_mirror": True,

@@ -1,20 +1,21 @@
 """Spatial augmentation on the device (second half).
 
 `affine_sample` is scipy.ndimage.map_coordinates over an affine coordinate field (the compute core of batchgenerators'
-SpatialTransform as nnU-Net configures it, data_augmentation_moreDA.py:66-80), on `mt_spline_prefilter3` / `mt_affine_sample`.
+SpatialTransform as nnU-Net configures it, data_augmentation_moreDA.py:66-80), on `mt_spline_prefilter3` / `mt_affine_sample`;
+`warp_sample` is the same over the mesh displaced by an elastic field (`mt_warp_sample`), and `gaussian_filter_zero_device` is the
+zero-padded Gaussian that batchgenerators' elastic_deform_coordinates smooths its noise with (`mt_gaussian_blur_axis_zero`).
 `SpatialTransformDevice` draws the per-sample rotation / scaling like batchgenerators' `augment_spatial` (third party, absent in
 the build container: restated from its published source, batchgenerators>=0.23 — parity UNPINNED; the kernels themselves are
-pinned against scipy in tests/test_spatial_gpu.py) and hands the matrices to the kernels; `MirrorTransformDevice` is the last
-spatial step of the chain (data_augmentation_moreDA.py:108-109)."""
+pinned against scipy in tests/test_spatial_gpu.py and tests/test_elastic_gpu.py) and hands the matrices to the kernels;
+`MirrorTransformDevice` is the last spatial step of the chain (data_augmentation_moreDA.py:108-109)."""
 import numpy as np
 import torch
 
 from ... import _lib
 
 
-def affine_sample(x, mats, out_shape, order, cval=0.0, is_seg=False, planar=False):
-    """x: [N, C, D, H, W] float32 device tensor; mats: [N, 12] (row-major 3x3 M then the centre) so that output voxel o reads
-    input coordinate M (o - (O-1)/2) + centre; order 0 / 1 / 3; is_seg with order 1 = batchgenerators' per-label rule."""
+def _sampler_source(x, mats, order, is_seg, planar):
+    """the (source, mode, mats) of one sampling call: order 3 samples the prefiltered B-spline coefficients."""
     assert x.is_cuda and x.dim() == 5 and x.dtype == torch.float32
     lib = _lib.load()
     st = torch.cuda.current_stream(x.device).cuda_stream
@@ -31,10 +32,75 @@ def affine_sample(x, mats, out_shape, order, cval=0.0, is_seg=False, planar=Fals
         src, mode = x.contiguous(), 0
     else:
         raise NotImplementedError("interpolation order %d (is_seg=%s) is not on the device path" % (order, is_seg))
+    return src, mode, mats
+
+
+def affine_sample(x, mats, out_shape, order, cval=0.0, is_seg=False, planar=False):
+    """x: [N, C, D, H, W] float32 device tensor; mats: [N, 12] (row-major 3x3 M then the centre) so that output voxel o reads
+    input coordinate M (o - (O-1)/2) + centre; order 0 / 1 / 3; is_seg with order 1 = batchgenerators' per-label rule."""
+    src, mode, mats = _sampler_source(x, mats, order, is_seg, planar)
+    N, C, D, H, W = (int(i) for i in x.shape)
+    st = torch.cuda.current_stream(x.device).cuda_stream
     out = torch.empty((N, C) + tuple(int(i) for i in out_shape), dtype=torch.float32, device=x.device)
-    _lib.check(lib.mt_affine_sample(src.data_ptr(), N, C, D, H, W, out.data_ptr(), out.shape[2], out.shape[3], out.shape[4],
-                                    mats.data_ptr(), mode, float(cval), 1 if planar else 0, st), 'affine_sample')
+    _lib.check(_lib.load().mt_affine_sample(src.data_ptr(), N, C, D, H, W, out.data_ptr(), out.shape[2], out.shape[3], out.shape[4],
+                                            mats.data_ptr(), mode, float(cval), 1 if planar else 0, st), 'affine_sample')
     return out
+
+
+def warp_sample(x, mats, out_shape, order, field, alpha, cval=0.0, is_seg=False, planar=False):
+    """affine_sample over the displaced mesh: output voxel o reads M (o - (O-1)/2 + alpha[n] field[n, :, o]) + centre.
+    field: [N, 3, OD, OH, OW] float32 device tensor (planar: [N, 2, OH, OW], one field for all slices); alpha: [N].  A sample
+    with alpha 0 never reads its field."""
+    src, mode, mats = _sampler_source(x, mats, order, is_seg, planar)
+    N, C, D, H, W = (int(i) for i in x.shape)
+    out_shape = tuple(int(i) for i in out_shape)
+    assert field.is_cuda and field.dtype == torch.float32 and field.is_contiguous()
+    assert tuple(field.shape) == ((N, 2) + out_shape[1:] if planar else (N, 3) + out_shape), tuple(field.shape)
+    alpha = torch.as_tensor(np.asarray(alpha, dtype=np.float32)).to(x.device) if not torch.is_tensor(alpha) else alpha.float().to(x.device)
+    alpha = alpha.contiguous()
+    assert tuple(alpha.shape) == (N,)
+    st = torch.cuda.current_stream(x.device).cuda_stream
+    out = torch.empty((N, C) + out_shape, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().mt_warp_sample(src.data_ptr(), N, C, D, H, W, out.data_ptr(), out_shape[0], out_shape[1], out_shape[2],
+                                          mats.data_ptr(), field.data_ptr(), alpha.data_ptr(), mode, float(cval),
+                                          1 if planar else 0, st), 'warp_sample')
+    return out
+
+
+ZERO_BLUR_MAX_RADIUS = 64          # mt_gaussian_blur_axis_zero refuses a larger radius int(4 sigma + 0.5): it never clamps
+
+
+def gaussian_filter_zero_device(x, sigma):
+    """scipy.ndimage.gaussian_filter(x[n, c], sigma[n, c], mode='constant', cval=0) (truncate 4) for every (sample, channel) of a
+    [N, C, D, H, W] device tensor; sigma <= 0 copies that channel.  Axis order D, H, W like scipy, every pass rounded to float32;
+    axes of length 1 are skipped, so [.., 1, H, W] is filtered like scipy filters the 2-D array.  The input is never written."""
+    assert x.is_cuda and x.dim() == 5 and x.dtype == torch.float32
+    N, C, D, H, W = (int(i) for i in x.shape)
+    sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float32), (N, C)).reshape(N * C))
+    ok = (sg <= 0) | (4.0 * sg.astype(np.float64) + 0.5 < ZERO_BLUR_MAX_RADIUS + 1)          # false for a NaN as well
+    if not ok.all():
+        raise ValueError("gaussian_filter_zero_device: sigma %s needs a radius above %d" % (sg[~ok], ZERO_BLUR_MAX_RADIUS))
+    lib = _lib.load()
+    st = torch.cuda.current_stream(x.device).cuda_stream
+    src = x.contiguous()
+    tmp = [torch.empty_like(src), torch.empty_like(src)]
+    cur, k = src, 0
+    for axis in range(3):
+        if src.shape[2 + axis] == 1:
+            continue
+        _lib.check(lib.mt_gaussian_blur_axis_zero(cur.data_ptr(), tmp[k].data_ptr(), N * C, D, H, W, axis,
+                                                  sg.ctypes.data_as(_lib.c_float_p), st), 'gaussian_blur_axis_zero')
+        cur, k = tmp[k], 1 - k
+    return cur if cur is not src else src.clone()
+
+
+def elastic_noise(seed, ndim, patch, device):
+    """the noise of one sample's elastic field, [ndim, 1, *patch] in 2 U[0, 1) - 1, float32, from a device generator seeded with
+    `seed`.  DEVIATION from the reference: elastic_deform_coordinates consumes ndim * |patch| draws of numpy's global stream per
+    deformed sample, the device path consumes ONE (the seed) and draws the noise on the device."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    return torch.rand((ndim, 1) + tuple(int(i) for i in patch), generator=gen, device=device, dtype=torch.float32) * 2 - 1
 
 
 def rotation_matrix_3d(angle_x, angle_y, angle_z):
@@ -48,17 +114,21 @@ def rotation_matrix_3d(angle_x, angle_y, angle_z):
 
 class SpatialTransformDevice:
     """Rotation + scaling + (centre | random) crop to `patch_size` in one resampling pass per sample.  Parameter names and
-    defaults follow batchgenerators.transforms.spatial_transforms.SpatialTransform as called by get_moreDA_augmentation;
-    elastic deformation (off in nnU-Net's 3D defaults) is not on this path."""
+    defaults follow batchgenerators.transforms.spatial_transforms.SpatialTransform as called by get_moreDA_augmentation.
+    Elastic deformation (off in nnU-Net's 3D defaults): a sample that draws it gets the mesh offsets alpha * gaussian_filter(noise,
+    sigma, 'constant') of elastic_deform_coordinates before the rotation; `last_elastic` keeps the last batch's per-sample
+    (alpha, sigma, seed) or None, from which the field can be rebuilt (elastic_noise -> gaussian_filter_zero_device), and
+    `last_mats` its [B, 12] matrices."""
 
     def __init__(self, patch_size, patch_center_dist_from_border=30, do_elastic_deform=False, do_rotation=True,
                  angle_x=(0, 2 * np.pi), angle_y=(0, 2 * np.pi), angle_z=(0, 2 * np.pi), do_scale=True, scale=(0.75, 1.25),
                  border_mode_data='constant', border_cval_data=0, order_data=3, border_mode_seg='constant', border_cval_seg=0,
                  order_seg=1, random_crop=False, p_el_per_sample=1, p_scale_per_sample=1, p_rot_per_sample=1,
-                 independent_scale_for_each_axis=False, p_rot_per_axis=1, p_independent_scale_per_axis=1, dummy_2d=False):
+                 independent_scale_for_each_axis=False, p_rot_per_axis=1, p_independent_scale_per_axis=1, dummy_2d=False,
+                 alpha=(0., 1000.), sigma=(10., 13.)):
         self.dummy_2d = dummy_2d              # Convert3DTo2DTransform around the transform (data_augmentation_moreDA.py:57-82)
-        if do_elastic_deform:
-            raise NotImplementedError("elastic deformation is not on the device path (off in nnU-Net's 3D defaults)")
+        self.do_elastic, self.p_el, self.alpha, self.sigma = bool(do_elastic_deform), p_el_per_sample, alpha, sigma
+        self.last_elastic = self.last_mats = None
         if border_mode_data != 'constant' or border_mode_seg != 'constant':
             raise NotImplementedError("only constant borders (nnU-Net's setting) are on the device path")
         self.patch_size = tuple(int(i) for i in patch_size)
@@ -71,9 +141,17 @@ class SpatialTransformDevice:
         self.indep, self.p_indep = independent_scale_for_each_axis, p_independent_scale_per_axis
 
     def draw(self, in_shape):
-        """one sample's (M, centre, modified) with numpy's global random stream, in augment_spatial's call order."""
+        """one sample's (M, centre, modified) with numpy's global random stream, in augment_spatial's call order.  The elastic
+        draw comes first (u < p_el, then alpha, sigma and one integer seed for the device noise) and is left in
+        `self._drawn_elastic`; without do_elastic_deform nothing is drawn for it."""
         m, modified = np.eye(3), False
         nd = 2 if self.dummy_2d else 3
+        self._drawn_elastic = None
+        if self.do_elastic and np.random.uniform() < self.p_el:
+            a = np.random.uniform(self.alpha[0], self.alpha[1])
+            sg = np.random.uniform(self.sigma[0], self.sigma[1])
+            self._drawn_elastic = (a, sg, int(np.random.randint(0, 2 ** 31 - 1)))
+            modified = True
         if self.do_rotation and np.random.uniform() < self.p_rot:
             if self.dummy_2d:                 # 2D: one angle (angle_x), coords @ [[c, -s], [s, c]]
                 a = np.random.uniform(*self.angles[0]) if np.random.uniform() <= self.p_rot_axis else 0
@@ -106,8 +184,10 @@ class SpatialTransformDevice:
         B = data.shape[0]
         in_shape = tuple(int(i) for i in data.shape[2:])
         mats = np.zeros((B, 12), dtype=np.float32)
+        elastic = [None] * B
         for b in range(B):
             m, ctr, modified = self.draw(in_shape)
+            elastic[b] = self._drawn_elastic
             if not modified and not self.random_crop:
                 # batchgenerators centre-crops without interpolation: integer lower corner (s - p) // 2
                 ctr = np.array([(in_shape[d] - self.patch_size[d]) // 2 + (self.patch_size[d] - 1) / 2. for d in range(3)])
@@ -117,11 +197,35 @@ class SpatialTransformDevice:
         if self.dummy_2d:
             assert in_shape[0] == self.patch_size[0], "dummy 2D: the loader patch keeps the slice axis (nnUNetTrainerV2.py:374-379)"
             mats[:, 9] = 0
-        out = affine_sample(data, mats, self.patch_size, self.order_data, self.cval_data, planar=self.dummy_2d)
+        self.last_elastic, self.last_mats = elastic, mats
+        if all(e is None for e in elastic):
+            out = affine_sample(data, mats, self.patch_size, self.order_data, self.cval_data, planar=self.dummy_2d)
+            out_seg = None
+            if seg is not None:
+                out_seg = affine_sample(seg, mats, self.patch_size, self.order_seg, self.cval_seg, is_seg=True, planar=self.dummy_2d)
+            return out, out_seg
+        field, alpha = self.elastic_field(elastic, data.device)
+        out = warp_sample(data, mats, self.patch_size, self.order_data, field, alpha, self.cval_data, planar=self.dummy_2d)
         out_seg = None
         if seg is not None:
-            out_seg = affine_sample(seg, mats, self.patch_size, self.order_seg, self.cval_seg, is_seg=True, planar=self.dummy_2d)
+            out_seg = warp_sample(seg, mats, self.patch_size, self.order_seg, field, alpha, self.cval_seg, is_seg=True, planar=self.dummy_2d)
         return out, out_seg
+
+    def elastic_field(self, elastic, device):
+        """per-sample (alpha, sigma, seed) or None -> (field [B, ndim, patch], alpha [B]) as warp_sample takes them: the noise of
+        the samples that drew elastic is filtered as one [n_el * ndim, 1, patch] tensor and scattered into the field; the other
+        samples get alpha 0 and a field that is never read."""
+        nd = 2 if self.dummy_2d else 3
+        patch = ((1,) + self.patch_size[1:]) if self.dummy_2d else self.patch_size      # dummy 2D: one (H, W) field for all slices
+        idx = [b for b, e in enumerate(elastic) if e is not None]
+        noise = torch.cat([elastic_noise(elastic[b][2], nd, patch, device) for b in idx])
+        sg = np.repeat(np.array([elastic[b][1] for b in idx], dtype=np.float32), nd)[:, None]
+        smooth = gaussian_filter_zero_device(noise, sg)                                 # [n_el * nd, 1, *patch]
+        shape = self.patch_size[1:] if self.dummy_2d else self.patch_size
+        field = torch.empty((len(elastic), nd) + shape, dtype=torch.float32, device=device)
+        field[torch.as_tensor(idx, device=device)] = smooth.reshape((len(idx), nd) + shape)
+        alpha = np.array([e[0] if e is not None else 0.0 for e in elastic], dtype=np.float32)
+        return field, alpha
 
 
 class MirrorTransformDevice:

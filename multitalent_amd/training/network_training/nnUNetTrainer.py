@@ -687,7 +687,10 @@ class nnUNetTrainerV2(nnUNetTrainer):
     def setup_augmentation_params(self):
         """nnUNetTrainerV2.setup_DA_params (:352-389): +-30 degree rotations (+-180 in-plane for the dummy-2D mode of anisotropic
         patches), scale (0.7, 1.4), no elastic deformation; the loader patch is computed BEFORE the scale override, i.e. with
-        the default (0.85, 1.25) — a quirk of the reference that is kept."""
+        the default (0.85, 1.25) — a quirk of the reference that is kept.  A subclass turns elastic deformation on by overriding
+        this method and setting `do_elastic` on the returned dict (its alpha / sigma ranges are set here: the 3D defaults, or
+        default_2D_augmentation_params' under the dummy-2D mode, :361-364).  `mask_was_used_for_normalization` hands the plans'
+        use_mask_for_norm to the chain's MaskTransform (data_augmentation_moreDA.py:113-115)."""
         from ..data_augmentation.color import default_3d_augmentation_params
         from ..data_augmentation.spatial import get_patch_size
         p = default_3d_augmentation_params()
@@ -695,10 +698,12 @@ class nnUNetTrainerV2(nnUNetTrainer):
         if getattr(self, 'do_dummy_2D_aug', False):
             p['dummy_2D'] = True
             p['rotation_x'] = (-np.pi, np.pi)                      # default_2D_augmentation_params['rotation_x']
+            p['elastic_deform_alpha'], p['elastic_deform_sigma'] = (0., 200.), (9., 13.)      # default_2D_augmentation_params
             self.basic_generator_patch_size = np.array([ps[0]] + list(get_patch_size(ps[1:], p['rotation_x'], p['rotation_y'],
                                                                                      p['rotation_z'], (0.85, 1.25))))
         else:
             self.basic_generator_patch_size = get_patch_size(ps, p['rotation_x'], p['rotation_y'], p['rotation_z'], (0.85, 1.25))
+        p['mask_was_used_for_normalization'] = getattr(self, 'use_mask_for_norm', None)
         self.data_aug_params.update(p)
         return p
 

@@ -1,10 +1,19 @@
-"""Device augmentation throughput at the benchmark patch: loader-sized batch (B=2, basic_generator_patch_size) -> 48x192x192."""
-import sys, os, time
+"""Device augmentation throughput at the benchmark patch: loader-sized batch (B=2, basic_generator_patch_size) -> 48x192x192.
+--elastic adds the elastic-deformation leg (every sample deformed, sigma 13 = radius 52, the widest filter of the reference's range):
+the whole call and its stages apart (noise, the three blur passes, the warp) by device events; --host adds the reference's
+computation of the same shape with scipy in float64 (3 x gaussian_filter + map_coordinates per sample); --json FILE keeps the
+measured lines."""
+import argparse, json, sys, os, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import numpy as np
 import torch
 from multitalent_amd.training.data_augmentation.spatial import SpatialTransformDevice, MirrorTransformDevice, get_patch_size
 from multitalent_amd.training.data_augmentation.color import default_3d_augmentation_params, GammaDevice
+ap = argparse.ArgumentParser()
+ap.add_argument('--elastic', action='store_true')
+ap.add_argument('--host', action='store_true')
+ap.add_argument('--json', default=None)
+args = ap.parse_args()
 dev = torch.device('cuda:0')
 p = default_3d_augmentation_params()
 ps = (48, 192, 192)
@@ -26,3 +35,73 @@ for _ in range(n):
     d2 = gm(d.clone()); mr(d2, g.clone())
 torch.cuda.synchronize()
 print('gamma (retain stats) + mirror on every sample: %.2f ms per batch' % ((time.time() - t) / n * 1e3))
+lines = [{'leg': 'spatial', 'loader_patch': list(bps), 'patch': list(ps), 'batch': 2, 'ms_per_batch': dt * 1e3}]
+
+
+def timed(fn, n=10, warm=2):
+    """median and spread of n device-event timings of fn() after `warm` untimed calls, in ms."""
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); fn(); b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts)), float(min(ts)), float(max(ts))
+
+
+if args.elastic:
+    from multitalent_amd import _lib
+    from multitalent_amd.training.data_augmentation.spatial import elastic_noise, warp_sample
+    HBM_PEAK = 8.0e12                     # bytes/s, the MI355X's specified HBM3E peak
+    el = SpatialTransformDevice(ps, angle_x=p['rotation_x'], angle_y=p['rotation_y'], angle_z=p['rotation_z'], scale=p['scale_range'],
+                                p_rot_per_sample=1.0, p_scale_per_sample=1.0, border_cval_seg=-1, do_elastic_deform=True,
+                                p_el_per_sample=1.0, alpha=p['elastic_deform_alpha'], sigma=(13., 13.))
+    np.random.seed(0)
+    med, lo, hi = timed(lambda: el(x, s))
+    print('elastic, every sample deformed (sigma 13, radius 52) + rotated + scaled: %.2f ms per batch (min %.2f, max %.2f; %.0f patches/s)'
+          % (med, lo, hi, 2e3 / med))
+    lines.append({'leg': 'elastic_whole_call', 'ms_per_batch': med, 'min_ms': lo, 'max_ms': hi})
+    seeds = [e[2] for e in el.last_elastic]
+    med, lo, hi = timed(lambda: torch.cat([elastic_noise(sd, 3, ps, dev) for sd in seeds]))
+    print('  noise (2 x 3 x patch, seeded device generator): %.3f ms (min %.3f, max %.3f)' % (med, lo, hi))
+    lines.append({'leg': 'elastic_noise', 'ms': med, 'min_ms': lo, 'max_ms': hi})
+    noise = torch.cat([elastic_noise(sd, 3, ps, dev) for sd in seeds])
+    tmp = torch.empty_like(noise)
+    sg = np.full(6, 13., dtype=np.float32)
+    lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
+    nbytes = 2 * 4 * noise.numel()          # one read and one write per element
+    for axis, name in enumerate('DHW'):
+        med, lo, hi = timed(lambda: _lib.check(lib.mt_gaussian_blur_axis_zero(noise.data_ptr(), tmp.data_ptr(), 6, ps[0], ps[1], ps[2], axis,
+                                                                              sg.ctypes.data_as(_lib.c_float_p), stream), 'blur'))
+        print('  blur pass along %s (6 channels of %s, 105 taps): %.3f ms (min %.3f, max %.3f) = %.2f TB/s of one read + one write, %.0f %% of the %.1f TB/s HBM peak'
+              % (name, ps, med, lo, hi, nbytes / med * 1e-9, 100 * nbytes / (med * 1e-3) / HBM_PEAK, HBM_PEAK * 1e-12))
+        lines.append({'leg': 'elastic_blur_' + name, 'ms': med, 'min_ms': lo, 'max_ms': hi, 'bytes': nbytes,
+                      'bytes_per_s': nbytes / (med * 1e-3), 'share_of_hbm_peak': nbytes / (med * 1e-3) / HBM_PEAK})
+    field, alpha = el.elastic_field(el.last_elastic, dev)
+    mats = el.last_mats
+    med, lo, hi = timed(lambda: (warp_sample(x, mats, ps, 3, field, alpha, 0), warp_sample(s, mats, ps, 1, field, alpha, -1, is_seg=True)))
+    print('  warp (prefilter + order-3 data, per-label order-1 seg): %.2f ms (min %.2f, max %.2f)' % (med, lo, hi))
+    lines.append({'leg': 'elastic_warp', 'ms': med, 'min_ms': lo, 'max_ms': hi})
+    if args.host:
+        from scipy import ndimage
+        rs = np.random.RandomState(0)
+        xh = x[0, 0].cpu().numpy().astype(np.float64)
+        t0 = time.time()
+        off = [ndimage.gaussian_filter(rs.random_sample(ps) * 2 - 1, 13., mode='constant', cval=0) * 450. for _ in range(3)]
+        t1 = time.time()
+        g = np.stack(np.meshgrid(*[np.arange(k) - (k - 1) / 2. for k in ps], indexing='ij')) + np.stack(off)
+        m, ctr = mats[0, :9].reshape(3, 3).astype(np.float64), mats[0, 9:].astype(np.float64)
+        co = (m @ g.reshape(3, -1) + ctr[:, None]).reshape((3,) + ps)
+        t2 = time.time()
+        ndimage.map_coordinates(xh, co, order=3, mode='constant', cval=0.0)
+        t3 = time.time()
+        print('  host, scipy float64, ONE sample: 3 x gaussian_filter %.0f ms + map_coordinates(order 3) %.0f ms = %.0f ms (a batch of 2: %.0f ms)'
+              % ((t1 - t0) * 1e3, (t3 - t2) * 1e3, (t1 - t0 + t3 - t2) * 1e3, 2 * (t1 - t0 + t3 - t2) * 1e3))
+        lines.append({'leg': 'elastic_host_scipy_float64_per_sample', 'gaussian_filter_x3_ms': (t1 - t0) * 1e3,
+                      'map_coordinates_ms': (t3 - t2) * 1e3})
+if args.json:
+    with open(args.json, 'w') as f:
+        for l in lines:
+            f.write(json.dumps(l) + '\n')
