@@ -544,6 +544,48 @@ int mt_label_counts(const float* seg, long V, const uint8_t* table, int L, int n
 int mt_label_locations(const float* seg, int D, int H, int W, const uint8_t* table, int L, int nslots, void* ws, size_t ws_bytes,
                        int32_t* idx, long idx_capacity, const int32_t* qslot, const int64_t* qrank, long nq, int64_t* out,
                        mt_stream_t stream);
+/* Intensity augmentation of the training chain (data_augmentation_moreDA.py:90-106: BrightnessMultiplicativeTransform,
+ * ContrastAugmentationTransform, the inverted and the plain GammaTransform; training/data_augmentation/color.py).  Additions to ABI 4.
+ * Both calls work on a contiguous float32 batch x[NC][V] (the [N, C, D, H, W] batch, NC = N*C, every channel volume contiguous;
+ * with NC = N, V = C*V the same calls treat a whole sample as one channel).  Nothing is read back: the statistics stay in device
+ * memory, the parameters drawn on the host travel in the kernel arguments.  V > INT32_MAX is MT_EINVAL before any launch.
+ * mt_channel_stats: for every channel c with active[c] != 0 (HOST bytes, NC of them; NULL = all)
+ *   stats[c] (device doubles, [NC][4]) = min, max, mean, population standard deviation (ddof 0) of x[c].  An inactive channel is not
+ *   read and its row of stats is not written.  Min and max are exact.  ONE pass over the data (4 bytes per element), all channels in
+ *   one launch: the sums are those of the SHIFTED values d = x - x[c][0], sum(d) and sum(d*d) in double, mean = x[c][0] + sum(d)/V,
+ *   variance = (sum(d*d) - sum(d)^2/V)/V.  The shift is a sample of the channel, so (shift - mean)^2 <= V * variance and the
+ *   subtraction loses at most log2(V) <= 31 of the 53 bits: a channel whose mean is 100 times (or 10^6 times) its sd keeps its sd.
+ *   Per-workgroup partials are combined in a fixed order by a second small launch, no floating-point atomics: bit-identical from
+ *   run to run.  A constant channel gives sd 0 exactly.  NaN elements are outside the contract.
+ *   ws: mt_channel_stats_workspace(NC, V) bytes of device scratch, 8-byte aligned; a smaller one is MT_EINVAL before any launch.
+ * mt_intensity_apply: in place, one launch per 64 channels.  records: HOST array of NC mt_intensity_op_t, one per channel:
+ *   MT_INTENSITY_NONE      the channel is neither read nor written;
+ *   MT_INTENSITY_SCALE     x *= a                                                    (brightness, :90; needs no statistics)
+ *   MT_INTENSITY_CONTRAST  x = (x - mean) * a + mean, then clamped to [min, max] when flags has MT_INTENSITY_PRESERVE_RANGE    (:91)
+ *   MT_INTENSITY_GAMMA     with y = -x when flags has MT_INTENSITY_NEGATE (invert_image, :104), else x, and min / max of y derived
+ *                          from those of x (min <-> -max):  y = ((y - min) / (max - min + b))^a * (max - min) + min,  b = epsilon;
+ *                          -y is stored when negated                                                                (:104-106)
+ *   MT_INTENSITY_RESTORE   retain_stats of the same transforms: y = (y - mean1) / (sd1 + 1e-8) * sd0 + mean0 in the same (negated)
+ *                          domain, (mean0, sd0) from stats[c] (taken before the gamma), (mean1, sd1) from stats2[c] (taken after it).
+ *   stats, stats2: device arrays of mt_channel_stats written earlier on the same stream (NULL where no record needs them: SCALE and
+ *   NONE need none, only RESTORE needs stats2).  All arithmetic is float32 in the order written, every operation rounded on its own,
+ *   true divisions; the statistics are rounded to float32 once.  A constant channel (range 0, sd 0) gives what the formulas give,
+ *   finite values; the base of the power is >= 0 by construction and 0^a = 0.  The op is uniform per workgroup, so a launch that mixes
+ *   ops does not make the scaled channels pay for the power.  An unknown op, or a record whose statistics are NULL, is MT_EINVAL
+ *   before any launch. */
+#define MT_INTENSITY_NONE 0
+#define MT_INTENSITY_SCALE 1
+#define MT_INTENSITY_CONTRAST 2
+#define MT_INTENSITY_GAMMA 3
+#define MT_INTENSITY_RESTORE 4
+#define MT_INTENSITY_PRESERVE_RANGE 1
+#define MT_INTENSITY_NEGATE 2
+typedef struct { int32_t op, flags; float a, b; } mt_intensity_op_t;
+size_t mt_channel_stats_workspace(int NC, long V);
+int mt_channel_stats(const float* x, int NC, long V, const uint8_t* active /* host, NC, or NULL */, double* stats /* [NC][4] */,
+                     void* ws, size_t ws_bytes, mt_stream_t stream);
+int mt_intensity_apply(float* x, int NC, long V, const mt_intensity_op_t* records /* host, NC */, const double* stats,
+                       const double* stats2, mt_stream_t stream);
 /* Evaluation (evaluation/evaluator.py, evaluation/metrics.py:314-383).
  * mt_seg_joint_hist: one pass over two contiguous uint8 label volumes of V voxels (any alignment; V is not limited to int32):
  *   hist[remap[test[v]] * C + remap[ref[v]]] += 1, exact 64-bit counts in the device array hist[C * C] (zeroed by the call).

@@ -60,6 +60,12 @@ class mt_patch_src_t(C.Structure):
     _fields_ = [('data', C.c_void_p), ('seg', C.c_void_p), ('shape', C.c_int32 * 3), ('lb', C.c_int32 * 3)]
 
 
+class mt_intensity_op_t(C.Structure):
+    _fields_ = [('op', C.c_int32), ('flags', C.c_int32), ('a', C.c_float), ('b', C.c_float)]
+
+
+MT_INTENSITY_NONE, MT_INTENSITY_SCALE, MT_INTENSITY_CONTRAST, MT_INTENSITY_GAMMA, MT_INTENSITY_RESTORE = 0, 1, 2, 3, 4
+MT_INTENSITY_PRESERVE_RANGE, MT_INTENSITY_NEGATE = 1, 2
 MT_F32, MT_BF16, MT_F16 = 0, 1, 2
 MT_PATCH_MAX_SRC = 16
 MT_PAD_CONSTANT, MT_PAD_EDGE = 0, 1
@@ -145,6 +151,9 @@ SIGNATURES = {
     'mt_masked_moments_workspace': (_sz, [_i, _l]),
     'mt_masked_moments': (_i, [_vp, _i, _l, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'mt_intensity_normalize': (_i, [_vp, _l, _i, _f, _f, _f, _f, _vp, _f, _vp, _vp]),
+    'mt_channel_stats_workspace': (_sz, [_i, _l]),
+    'mt_channel_stats': (_i, [_vp, _i, _l, _vp, _vp, _vp, _sz, _vp]),
+    'mt_intensity_apply': (_i, [_vp, _i, _l, _P(mt_intensity_op_t), _vp, _vp, _vp]),
     'mt_label_counts_workspace': (_sz, [_l, _i]),
     'mt_label_counts': (_i, [_vp, _l, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     'mt_label_locations': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp, _l, _vp, _vp, _l, _vp, _vp]),

@@ -888,6 +888,61 @@ def intensity_normalize(x, clip=None, mean=0.0, sd=1.0, stats=None, eps=0.0, seg
     return x
 
 
+_AUG = "the intensity augmentation runs"
+INTENSITY_NONE, INTENSITY_SCALE, INTENSITY_CONTRAST, INTENSITY_GAMMA, INTENSITY_RESTORE = (
+    _lib.MT_INTENSITY_NONE, _lib.MT_INTENSITY_SCALE, _lib.MT_INTENSITY_CONTRAST, _lib.MT_INTENSITY_GAMMA, _lib.MT_INTENSITY_RESTORE)
+INTENSITY_PRESERVE_RANGE, INTENSITY_NEGATE = _lib.MT_INTENSITY_PRESERVE_RANGE, _lib.MT_INTENSITY_NEGATE
+INTENSITY_OP_DTYPE = np.dtype([('op', np.int32), ('flags', np.int32), ('a', np.float32), ('b', np.float32)])     # mt_intensity_op_t
+
+
+def _channel_batch(x, who):
+    """(NC, V) of a contiguous float32 device batch: [N, C, D, H, W] (NC = N*C) or [NC, V]."""
+    _require_device(_AUG, x)
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    if x.dim() not in (2, 5) or x.numel() == 0:
+        raise ValueError("%s: a non-empty [N, C, D, H, W] or [NC, V] batch is expected, got shape %s" % (who, tuple(x.shape)))
+    NC = int(x.shape[0]) if x.dim() == 2 else int(x.shape[0]) * int(x.shape[1])
+    return NC, int(x.numel()) // NC
+
+
+def channel_stats(x, active=None, stats=None):
+    """x: [N, C, D, H, W] or [NC, V] float32 device batch (contiguous).  -> stats, float64 device tensor [NC, 4] = min, max, mean,
+    population sd of every channel whose entry of the host array `active` (NC booleans; None = all) is set; the other rows of a
+    given `stats` are left as they are.  One pass, deterministic; nothing is synchronised.  See mt_channel_stats."""
+    NC, V = _channel_batch(x, 'channel_stats')
+    act_ptr = None
+    if active is not None:
+        active = np.ascontiguousarray(np.asarray(active).reshape(-1) != 0, dtype=np.uint8)
+        if active.size != NC:
+            raise ValueError("channel_stats: %d activity flags for %d channels" % (active.size, NC))
+        act_ptr = active.ctypes.data_as(C.c_void_p)
+    if stats is None:
+        stats = torch.empty((NC, 4), dtype=torch.float64, device=x.device)
+    _require_device(_AUG, stats)
+    assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == NC * 4
+    lib = _lib.load()
+    ws = torch.empty(int(lib.mt_channel_stats_workspace(NC, V)), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.mt_channel_stats(_ptr(x), NC, V, act_ptr, _ptr(stats), _ptr(ws), ws.numel(), _stream()), 'channel_stats')
+    return stats
+
+
+def intensity_apply(x, records, stats=None, stats2=None):
+    """In place on x ([N, C, D, H, W] or [NC, V] float32 device batch, contiguous): one op per channel from the host array `records`
+    (NC entries of INTENSITY_OP_DTYPE: op INTENSITY_*, flags, a, b), its statistics from `stats` / `stats2` ([NC, 4] float64 device
+    tensors of channel_stats, enqueued before on the same stream).  Nothing is synchronised.  See mt_intensity_apply."""
+    NC, V = _channel_batch(x, 'intensity_apply')
+    records = np.ascontiguousarray(np.asarray(records, dtype=INTENSITY_OP_DTYPE).reshape(-1))
+    if records.size != NC:
+        raise ValueError("intensity_apply: %d records for %d channels" % (records.size, NC))
+    for s in (stats, stats2):
+        if s is not None:
+            _require_device(_AUG, s)
+            assert s.dtype == torch.float64 and s.is_contiguous() and s.numel() == NC * 4
+    _lib.check(_lib.load().mt_intensity_apply(_ptr(x), NC, V, records.ctypes.data_as(C.POINTER(_lib.mt_intensity_op_t)), _ptr(stats),
+                                              _ptr(stats2), _stream()), 'intensity_apply')
+    return x
+
+
 class LabelIndex:
     """State between label_counts and label_locations: the label map, the label-to-slot table and the unit offsets."""
 

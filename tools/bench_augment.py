@@ -12,6 +12,7 @@ from multitalent_amd.training.data_augmentation.color import default_3d_augmenta
 ap = argparse.ArgumentParser()
 ap.add_argument('--elastic', action='store_true')
 ap.add_argument('--host', action='store_true')
+ap.add_argument('--intensity', action='store_true')
 ap.add_argument('--json', default=None)
 args = ap.parse_args()
 dev = torch.device('cuda:0')
@@ -101,6 +102,145 @@ if args.elastic:
               % ((t1 - t0) * 1e3, (t3 - t2) * 1e3, (t1 - t0 + t3 - t2) * 1e3, 2 * (t1 - t0 + t3 - t2) * 1e3))
         lines.append({'leg': 'elastic_host_scipy_float64_per_sample', 'gaussian_filter_x3_ms': (t1 - t0) * 1e3,
                       'map_coordinates_ms': (t3 - t2) * 1e3})
+if args.intensity:
+    from multitalent_amd import ops
+    from multitalent_amd.training.data_augmentation import color
+    from multitalent_amd.training.data_augmentation.color import _range_pick
+    HBM_PEAK = 8.0e12                     # bytes/s, the MI355X's specified HBM3E peak
+
+    # The baseline leg: the torch formulation these transforms had before the kernels (per (sample, channel) loops of elementwise
+    # torch operations whose statistics are read to the host with float()), kept here only to be measured against.
+    class TorchBrightness:
+        def __init__(self, r=(0.75, 1.25), p=1.0):
+            self.r, self.p = r, p
+
+        def __call__(self, data):
+            for b in range(data.shape[0]):
+                if np.random.uniform() < self.p:
+                    for c in range(data.shape[1]):
+                        data[b, c] *= np.random.uniform(self.r[0], self.r[1])
+            return data
+
+    class TorchContrast:
+        def __init__(self, r=(0.75, 1.25), p=1.0):
+            self.r, self.p = r, p
+
+        def __call__(self, data):
+            for b in range(data.shape[0]):
+                if np.random.uniform() < self.p:
+                    for c in range(data.shape[1]):
+                        v = data[b, c]
+                        f = _range_pick(self.r[0], self.r[1])
+                        mn, lo, hi = v.mean(), v.min(), v.max()
+                        v.sub_(mn).mul_(f).add_(mn)
+                        v.clamp_(min=float(lo), max=float(hi))
+            return data
+
+    class TorchGamma:
+        def __init__(self, r=(0.7, 1.5), invert=False, p=1.0, eps=1e-7):
+            self.r, self.invert, self.p, self.eps = r, invert, p, eps
+
+        def __call__(self, data):
+            for b in range(data.shape[0]):
+                if np.random.uniform() < self.p:
+                    if self.invert:
+                        data[b].neg_()
+                    for c in range(data.shape[1]):
+                        v = data[b, c]
+                        mn, sd = float(v.mean()), float(v.std(unbiased=False))
+                        g = _range_pick(self.r[0], self.r[1])
+                        lo = float(v.min())
+                        rng = float(v.max()) - lo
+                        v.sub_(lo).div_(rng + self.eps).pow_(g).mul_(rng).add_(lo)
+                        v.sub_(float(v.mean()))
+                        v.div_(float(v.std(unbiased=False)) + 1e-8).mul_(sd).add_(mn)
+                    if self.invert:
+                        data[b].neg_()
+            return data
+
+    def chain(ts):
+        def run(d):
+            for t in ts:
+                d = t(d)
+            return d
+        return run
+
+    def one_call(fn, xw, x0):
+        """(device-event ms, host ms until fn returns) of fn(xw) on a fresh copy of x0 with an empty queue."""
+        xw.copy_(x0)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        a.record(); fn(xw); b.record()
+        host = (time.perf_counter() - t0) * 1e3
+        torch.cuda.synchronize()
+        return a.elapsed_time(b), host
+
+    def stat(v):
+        return {'median': float(np.median(v)), 'min': float(min(v)), 'max': float(max(v))}
+
+    ROUNDS, CALLS, WARM = 3, 10, 3
+    for Cn in (1, 4):
+        x0 = torch.randn((2, Cn) + ps, device=dev) * 2 + 1
+        xw = torch.empty_like(x0)
+        nel = x0.numel()
+        new = {'brightness': color.BrightnessMultiplicativeDevice(p_per_sample=1.), 'contrast': color.ContrastAugmentationDevice(p_per_sample=1.),
+               'gamma_inverted_retain_stats': color.GammaDevice(p['gamma_range'], True, True, True, 1.),
+               'gamma_retain_stats': color.GammaDevice(p['gamma_range'], False, True, True, 1.)}
+        old = {'brightness': TorchBrightness(), 'contrast': TorchContrast(), 'gamma_inverted_retain_stats': TorchGamma(p['gamma_range'], True),
+               'gamma_retain_stats': TorchGamma(p['gamma_range'], False)}
+        new['all_four'], old['all_four'] = chain(list(new.values())), chain(list(old.values()))
+        print('intensity transforms, B=2, C=%d, %s, every probability 1: %d rounds alternating kernels / torch formulation, %d calls each'
+              % (Cn, ps, ROUNDS, CALLS))
+        for name in new:
+            res = {'kernels': ([], [], []), 'torch': ([], [], [])}        # device ms, host ms, per-round medians of the device ms
+            for rnd in range(ROUNDS):
+                for leg, fn in (('kernels', new[name]), ('torch', old[name])):
+                    np.random.seed(rnd)
+                    for _ in range(WARM if rnd == 0 else 1):
+                        one_call(fn, xw, x0)
+                    ts = [one_call(fn, xw, x0) for _ in range(CALLS)]
+                    res[leg][0].extend(t[0] for t in ts); res[leg][1].extend(t[1] for t in ts)
+                    res[leg][2].append(float(np.median([t[0] for t in ts])))
+            line = {'leg': 'intensity_' + name, 'batch': 2, 'channels': Cn, 'patch': list(ps)}
+            for leg in res:
+                dv, ho = stat(res[leg][0]), stat(res[leg][1])
+                print('  %-28s %-7s device %.3f ms (min %.3f, max %.3f; round medians %s), host until return %.3f ms (min %.3f, max %.3f)'
+                      % (name, leg, dv['median'], dv['min'], dv['max'], ' '.join('%.3f' % m for m in res[leg][2]), ho['median'], ho['min'], ho['max']))
+                line[leg] = {'device_ms': dv, 'device_ms_round_medians': res[leg][2], 'host_ms_until_return': ho}
+            lines.append(line)
+        # the two kernels on their own, BURST calls back to back between one pair of events (an upper bound of the kernel time: it
+        # includes the launch gaps; rocprofv3 --kernel-trace gives the kernels alone).  Algorithmic bytes from the shape: 4 per
+        # element for a statistics pass, 8 for an apply pass.  The ops are chosen so that repeating them in place keeps the values
+        # in range (multiplier 1; the power maps [min, max] of the fixed statistics onto itself).
+        BURST = 20
+        st = ops.channel_stats(x0)
+        every = np.ones(2 * Cn, dtype=bool)
+
+        def records(op, a):
+            return color._records(every, op, np.full(2 * Cn, a), 0, 1e-7)
+        for kname, nbytes, fn in (('channel_stats', 4 * nel, lambda d: ops.channel_stats(d, None, st)),
+                                  ('apply_scale', 8 * nel, lambda d: ops.intensity_apply(d, records(ops.INTENSITY_SCALE, 1.))),
+                                  ('apply_gamma', 8 * nel, lambda d: ops.intensity_apply(d, records(ops.INTENSITY_GAMMA, 1.3), st)),
+                                  ('apply_restore', 8 * nel, lambda d: ops.intensity_apply(d, records(ops.INTENSITY_RESTORE, 0.), st, st))):
+            ts = []
+            for i in range(WARM + CALLS):
+                xw.copy_(x0)
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(BURST):
+                    fn(xw)
+                b.record()
+                torch.cuda.synchronize()
+                if i >= WARM:
+                    ts.append(a.elapsed_time(b) / BURST)
+            dv = stat(ts)
+            print('  kernel %-14s %.4f ms per call in bursts of %d (min %.4f, max %.4f) = %.2f TB/s of %d algorithmic bytes, %.0f %% of the %.1f TB/s HBM peak'
+                  % (kname, dv['median'], BURST, dv['min'], dv['max'], nbytes / dv['median'] * 1e-9, nbytes,
+                     100 * nbytes / (dv['median'] * 1e-3) / HBM_PEAK, HBM_PEAK * 1e-12))
+            lines.append({'leg': 'intensity_kernel_' + kname, 'batch': 2, 'channels': Cn, 'patch': list(ps), 'ms_per_call': dv, 'burst': BURST,
+                          'bytes': nbytes, 'bytes_per_s': nbytes / (dv['median'] * 1e-3), 'share_of_hbm_peak': nbytes / (dv['median'] * 1e-3) / HBM_PEAK})
 if args.json:
     with open(args.json, 'w') as f:
         for l in lines:
