@@ -469,6 +469,45 @@ int mt_resample_classify(const float* probs, int C, int D, int H, int W, int OD,
 int mt_ensemble_classify(const void* const* members, int K, int C, int D, int H, int W, long chan_stride,
                          const int32_t* class_order, int use_regions, uint8_t* out, long FD, long FH, long FW,
                          int bD, int bH, int bW, void* mean, long mean_stride, mt_stream_t stream);
+/* Label-map file writer: gzip / DEFLATE encoding on the device (replaces `sitk.WriteImage` of a .nii.gz label map,
+ * segmentation_export.py:148-160, and `gzip.open(..., compresslevel=1)` of utilities/nifti_io: raw voxels copied to the host and
+ * compressed by one thread).  The uncompressed stream is prefix[0, n_prefix) — a HOST array of at most MT_DEFLATE_MAX_PREFIX bytes,
+ * the 352 bytes of a NIfTI-1 header, so that the voxels are never copied or shifted on the device — followed by payload[0, n_payload)
+ * on the DEVICE (uint8, any alignment).  It is cut into chunks of `chunk` bytes (MT_DEFLATE_MIN_CHUNK .. MT_DEFLATE_MAX_CHUNK; the
+ * last may be shorter; an empty stream is one empty chunk) that are encoded independently, one workgroup each.
+ * Tokens: every maximal run of equal bytes inside a chunk is its first byte as a literal, then matches of (distance 1, length 258)
+ * while 258 bytes remain, then the remainder as one match when it is 3 or longer and as 1 or 2 literals otherwise; no match reaches
+ * across a chunk boundary.  The token stream is a function of the bytes and `chunk` alone.
+ * mt_deflate_tokenize: hist[0..285] = counts of the literal/length symbols of all chunks (one end-of-block per chunk included),
+ *   hist[286..315] = counts of the distance symbols (only symbol 0 occurs); DEVICE uint32[316], zeroed by the call.  Each chunk's
+ *   CRC-32 (IEEE) stays in the workspace for mt_deflate_emit.
+ * mt_deflate_emit: the same stream, prefix, chunk and workspace after mt_deflate_tokenize, plus the code the HOST built from hist:
+ *   table  HOST uint64[513]: a token's bits (first bit in bit 0, Huffman codes bit-reversed, extra bits behind their length code, the
+ *          distance code behind those) in bits 0..47 and their number in bits 48..63; entry b = literal b, 256 + (L - 3) = match of
+ *          length L, 512 = end of block;
+ *   header HOST uint32 words, header_bits bits: the dynamic block's header behind its BFINAL bit (BTYPE, HLIT, HDIST, HCLEN, the
+ *          code-length code, the coded lengths), unused high bits zero.
+ *   A chunk becomes one dynamic block: BFINAL (set in the last chunk only), header, tokens, end of block; every chunk but the last
+ *   is then byte-aligned by an empty stored block (3 zero bits, padding, 00 00 ff ff).  Where stored blocks (of up to 65535 bytes)
+ *   are smaller than that, the chunk is written as stored blocks instead, which end byte-aligned by themselves.  The raw DEFLATE
+ *   stream is the concatenation of the chunks.
+ *   out (DEVICE, 8-byte aligned, mt_deflate_bound bytes): int64 total, uint32 crc[nchunks], padding to 8 bytes, then the `total`
+ *   bytes of the DEFLATE stream.  The gzip framing (10-byte header, CRC-32 joined from the chunk CRCs, ISIZE) is the host's.
+ * mt_deflate_workspace / mt_deflate_bound: bytes of ws (16-byte aligned, caller-owned, no content expected) and of out for a
+ *   stream of n = n_prefix + n_payload bytes; both cover every chunk being stored; 0 for arguments the entry points refuse.
+ * Errors: n > INT32_MAX, a chunk or prefix size outside the limits, a token of more than 48 bits are MT_EINVAL, a short ws is
+ *   MT_EWORKSPACE, all before any launch.  Bits are written with integer atomic OR into zeroed words, tokens own disjoint bit
+ *   ranges: the output is bit-identical from run to run.  Nothing is synchronised. */
+#define MT_DEFLATE_MAX_PREFIX 512
+#define MT_DEFLATE_MIN_CHUNK 32
+#define MT_DEFLATE_MAX_CHUNK (1 << 24)
+size_t mt_deflate_workspace(long n, int chunk);
+size_t mt_deflate_bound(long n, int chunk);
+int mt_deflate_tokenize(const uint8_t* payload, long n_payload, const uint8_t* prefix /* host */, int n_prefix, int chunk,
+                        void* ws, size_t ws_bytes, uint32_t* hist /* device, 316 */, mt_stream_t stream);
+int mt_deflate_emit(const uint8_t* payload, long n_payload, const uint8_t* prefix /* host */, int n_prefix, int chunk,
+                    const uint64_t* table /* host, 513 */, const uint32_t* header /* host */, int header_bits,
+                    void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes, mt_stream_t stream);
 /* Connected-component post-processing (remove_all_but_the_largest_connected_component, postprocessing/connected_components.py:48-101).
  * mt_cc_label3d: `lmap, num_objects = scipy.ndimage.label(mask)` (:76) with scipy's default 3-D structure, 6-connectivity (face
  * neighbours only), on the mask {v : member[seg[v]] != 0} of a contiguous uint8 volume seg[D, H, W].  member: HOST array of 256

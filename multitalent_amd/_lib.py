@@ -69,6 +69,7 @@ MT_INTENSITY_PRESERVE_RANGE, MT_INTENSITY_NEGATE = 1, 2
 MT_F32, MT_BF16, MT_F16 = 0, 1, 2
 MT_PATCH_MAX_SRC = 16
 MT_PAD_CONSTANT, MT_PAD_EDGE = 0, 1
+MT_DEFLATE_MAX_PREFIX, MT_DEFLATE_MIN_CHUNK, MT_DEFLATE_MAX_CHUNK = 512, 32, 1 << 24
 MT_ABI_VERSION = 4
 MT_LABEL_SLOTS, MT_LABEL_UNLISTED = 1023, 0xffff
 MT_LABEL_DTYPES = {'uint8': 0, 'int8': 1, 'int16': 2, 'uint16': 3, 'int32': 4, 'uint32': 5, 'float32': 6, 'float64': 7}
@@ -142,6 +143,10 @@ SIGNATURES = {
     'mt_warp_sample': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp]),
     'mt_resample_classify': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _l, _l, _l, _i, _i, _i, _vp]),
     'mt_ensemble_classify': (_i, [_P(_vp), _i, _i, _i, _i, _i, _l, _vp, _i, _vp, _l, _l, _l, _i, _i, _i, _vp, _l, _vp]),
+    'mt_deflate_workspace': (_sz, [_l, _i]),
+    'mt_deflate_bound': (_sz, [_l, _i]),
+    'mt_deflate_tokenize': (_i, [_vp, _l, _vp, _i, _i, _vp, _sz, _vp, _vp]),
+    'mt_deflate_emit': (_i, [_vp, _l, _vp, _i, _i, _vp, _vp, _i, _vp, _sz, _vp, _sz, _vp]),
     'mt_cc_label3d': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'mt_cc_remove': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _i, _d, _vp, _vp]),
     'mt_nonzero_mask': (_i, [_vp, _i, _l, _vp, _vp]),

@@ -112,7 +112,7 @@ def _require_device():
     return torch
 
 
-def copy_and_convert_segmentation(segmentation, labels_in, labels_out, sanity_check=True, in_file=None):
+def copy_and_convert_segmentation(segmentation, labels_in, labels_out, sanity_check=True, in_file=None, keep_on_device=False):
     """:229-275.  segmentation: a numpy array (-> numpy uint8 array) or a device tensor (-> device uint8 tensor) in whatever type
     its file stores; int64 / uint64 are cast to float64 on the host, as `get_fdata` does.  A voxel not above 1e-20 (zero,
     negatives, NaN) becomes 0; a voxel that equals a listed label becomes that label's output (`label_table`); any other voxel
@@ -136,17 +136,17 @@ def copy_and_convert_segmentation(segmentation, labels_in, labels_out, sanity_ch
             seg = seg.double()
     if seg.numel() == 0:
         out = torch.zeros(seg.shape, dtype=torch.uint8, device=seg.device)
-        return out.cpu().numpy() if as_numpy else out
+        return out.cpu().numpy() if as_numpy and not keep_on_device else out
     out, count, smallest = ops.label_convert(seg, table)
     if sanity_check and count:
         raise RuntimeError("unexpected label in image %s: %r (%d voxels hold a value that is not among the expected labels %s)"
                            % (in_file, smallest, count, sorted(set(_flat_labels(labels_in)))))
-    return out.cpu().numpy() if as_numpy else out
+    return out.cpu().numpy() if as_numpy and not keep_on_device else out
 
 
 def copy_and_convert_segmentation_nifti(in_file, out_file, labels_in, labels_out, sanity_check=True):
     """:217-226 through utilities/nifti_io: the converted label file carries the input's geometry and is stored as uint8."""
-    _write_label(out_file, _convert_label(_read_label(in_file), in_file, labels_in, labels_out, sanity_check))
+    _write_label(out_file, _convert_label(_read_label(in_file), in_file, labels_in, labels_out, sanity_check, out_file.endswith('.nii.gz')))
 
 
 def _read_label(in_file):
@@ -154,13 +154,23 @@ def _read_label(in_file):
     return read_image(in_file)
 
 
-def _convert_label(img, in_file, labels_in, labels_out, sanity_check=True):
-    return copy_and_convert_segmentation(np.asarray(img.array), labels_in, labels_out, sanity_check, in_file), img
+def _convert_label(img, in_file, labels_in, labels_out, sanity_check=True, encode=False):
+    """-> (converted uint8 volume, img).  encode (the target is a .nii.gz): the volume stays on the device and is gzip-encoded there;
+    what comes back is the complete file as bytes, so that `_write_label` — a pool thread — only writes them."""
+    if not encode or np.ndim(img.array) != 3:
+        return copy_and_convert_segmentation(np.asarray(img.array), labels_in, labels_out, sanity_check, in_file), img
+    from ..utilities.nifti_io import encode_label_map_device
+    seg = copy_and_convert_segmentation(np.asarray(img.array), labels_in, labels_out, sanity_check, in_file, keep_on_device=True)
+    return encode_label_map_device(seg, img.GetSpacing(), img.GetOrigin(), img.GetDirection()), img
 
 
 def _write_label(out_file, converted):
     from ..utilities.nifti_io import write_image
     seg, img = converted
+    if isinstance(seg, bytes):
+        with open(out_file, 'wb') as f:
+            f.write(seg)
+        return
     write_image(seg, out_file, img.GetSpacing(), img.GetOrigin(), img.GetDirection())
 
 
@@ -231,7 +241,7 @@ def convert_task100(task_name="Task100_MultiTalent", tasks=None, num_threads=8, 
             if j + workers < len(jobs):                               # bounds the volumes waiting in host memory
                 reads.append(pool.submit(_read_label, jobs[j + workers][0]))
             copies += [pool.submit(shutil.copy, a, b) for a, b in to_copy[j * share:(j + 1) * share]]
-            writes.append(pool.submit(_write_label, dst, _convert_label(img, src, labels_in, labels_out)))
+            writes.append(pool.submit(_write_label, dst, _convert_label(img, src, labels_in, labels_out, encode=dst.endswith('.nii.gz'))))
             while len(writes) > 2 * workers:
                 writes.pop(0).result()
         copies += [pool.submit(shutil.copy, a, b) for a, b in to_copy[len(jobs) * share:]]

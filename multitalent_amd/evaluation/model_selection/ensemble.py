@@ -22,7 +22,7 @@ def merge(args):
     file1, file2, properties_file, out_file = args
     if not os.path.isfile(out_file):
         arrays, props, _ = _load_case([file1, file2], [properties_file])
-        seg, _ = merge_on_device(arrays, props[0], None)
+        seg, _ = merge_on_device(arrays, props[0], None, keep_on_device=out_file.endswith('.nii.gz'))
         write_image(seg, out_file, props[0]['itk_spacing'], props[0]['itk_origin'], props[0]['itk_direction'])
 
 

@@ -64,9 +64,10 @@ def upload_member(arr, device):
     return buf
 
 
-def merge_on_device(arrays, properties, regions_class_order=None, want_mean=False, device=None):
+def merge_on_device(arrays, properties, regions_class_order=None, want_mean=False, device=None, keep_on_device=False):
     """K float16 arrays [C, X, Y, Z] (X, Y, Z = size_after_cropping of `properties`) -> (uint8 label volume of
-    `original_size_of_raw_data` as numpy, float16 mean [C, X, Y, Z] as numpy or None)."""
+    `original_size_of_raw_data` as numpy — as a device tensor with `keep_on_device`, for the device file writer —, float16 mean
+    [C, X, Y, Z] as numpy or None)."""
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("multitalent_amd: ensembling runs on a HIP device only; there is no CPU fallback")
@@ -92,7 +93,7 @@ def merge_on_device(arrays, properties, regions_class_order=None, want_mean=Fals
     mean = torch.empty((C, cs), dtype=torch.float16, device=device) if want_mean else None
     ensemble_classify(members, C, shape, cs, out, lo, order_t, mean, cs)
     mean_np = mean[:, :V].cpu().numpy().reshape((C,) + shape) if want_mean else None
-    return out.cpu().numpy(), mean_np
+    return (out if keep_on_device else out.cpu().numpy()), mean_np
 
 
 def _load_pickle(f):
@@ -130,7 +131,7 @@ def merge_files(files, properties_files, out_file, override, store_npz, _loaded=
     from ..utilities.nifti_io import write_image
     if override or not os.path.isfile(out_file):
         arrays, props, regions_class_order = _loaded if _loaded is not None else _load_case(files, properties_files)
-        seg, mean = merge_on_device(arrays, props[0], regions_class_order, want_mean=store_npz)
+        seg, mean = merge_on_device(arrays, props[0], regions_class_order, want_mean=store_npz, keep_on_device=out_file.endswith('.nii.gz'))
         write_image(seg, out_file, props[0]['itk_spacing'], props[0]['itk_origin'], props[0]['itk_direction'])
         if store_npz:
             np.savez_compressed(out_file[:-7] + ".npz", softmax=mean)

@@ -16,7 +16,7 @@ import torch
 
 from ..dataset_conversion.Task100_MultiTalent import MultiTalent_region_output_idx_mapping, MultiTalent_regions
 from ..training.model_restore import load_model_and_checkpoint_files
-from .segmentation_export import save_segmentation_nifti_from_softmax
+from .segmentation_export import export_label_map_device
 
 
 def _export_params(trainer, segmentation_export_kwargs):
@@ -86,8 +86,9 @@ def predict_cases(model, list_of_lists, output_filenames, folds, save_npz, num_t
         for region in MultiTalent_regions.keys():
             ch = MultiTalent_region_output_idx_mapping[region]
             stem = os.path.join(dr, 'individual', f[:-7] + '_' + region)
-            save_segmentation_nifti_from_softmax(probs[ch:ch + 1], stem + '.nii.gz', dct, order, ((1,),), None, None,
-                                                 stem + '.npz' if save_npz else None, None, force_separate_z, order_z, verbose=False)
+            # 47 label maps per case: each is compressed on the device, only the .nii.gz bytes reach the host
+            export_label_map_device(probs[ch:ch + 1], stem + '.nii.gz', dct, order, ((1,),), stem + '.npz' if save_npz else None,
+                                    force_separate_z, order_z)
         print("inference done.")
 
 

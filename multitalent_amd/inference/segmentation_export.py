@@ -109,16 +109,22 @@ def resample_softmax(p, after, sep_axis):
     return q.permute(inv).contiguous()
 
 
-def save_segmentation_nifti_from_softmax(segmentation_softmax, out_fname, properties_dict, order=1, region_class_order=None,
-                                         seg_postprogess_fn=None, seg_postprocess_args=None, resampled_npz_fname=None,
-                                         non_postprocessed_fname=None, force_separate_z=None, interpolation_order_z=0, verbose=True):
-    """Same signature as the reference (segmentation_export.py:27-33).  Returns the uint8 array that is written.  Files are
-    written through SimpleITK when it is installed, otherwise by `utilities.nifti_io`'s NIfTI-1 writer; `resample_and_classify`
-    is the device-only core for callers with their own writer."""
-    import pickle
+def _write_label_map(seg, fname, properties_dict):
+    """seg: uint8 label map, device tensor or host array.  A device tensor going to a .nii.gz is compressed on the device
+    (utilities.nifti_io.write_label_map_device); anything else takes the host writer."""
     from ..utilities.nifti_io import write_image
-    if verbose:
-        print("force_separate_z:", force_separate_z, "interpolation order:", order)
+    if torch.is_tensor(seg) and not (seg.is_cuda and fname.endswith('.nii.gz')):
+        seg = seg.cpu().numpy()
+    if not torch.is_tensor(seg):
+        seg = seg.astype(np.uint8)
+    write_image(seg, fname, properties_dict['itk_spacing'], properties_dict['itk_origin'], properties_dict['itk_direction'])
+
+
+def _softmax_for_export(segmentation_softmax, properties_dict, order, region_class_order, resampled_npz_fname, force_separate_z,
+                        interpolation_order_z):
+    """the part of the export in front of the label map: a stored softmax file is loaded (and removed), the resampled
+    probabilities are stored as float16 + the properties pickle when `resampled_npz_fname` asks for them (:117-122)."""
+    import pickle
     if isinstance(segmentation_softmax, str):
         assert os.path.isfile(segmentation_softmax), "segmentation_softmax must point to an existing npy/npz file"
         del_file = deepcopy(segmentation_softmax)
@@ -142,15 +148,41 @@ def save_segmentation_nifti_from_softmax(segmentation_softmax, out_fname, proper
         with open(resampled_npz_fname[:-4] + ".pkl", 'wb') as f:
             pickle.dump(properties_dict, f)
         segmentation_softmax = p
+    return segmentation_softmax
+
+
+def export_label_map_device(segmentation_softmax, out_fname, properties_dict, order=1, region_class_order=None,
+                            resampled_npz_fname=None, force_separate_z=None, interpolation_order_z=0, verbose=False):
+    """`save_segmentation_nifti_from_softmax` for callers that do not look at the label map: resample, classify and write without
+    copying the raw voxels to the host — a `.nii.gz` is gzip-encoded on the device and only the compressed bytes come back.
+    -> the uint8 DEVICE tensor that was written.  No `seg_postprogess_fn` here: a host function needs the host array."""
+    if verbose:
+        print("force_separate_z:", force_separate_z, "interpolation order:", order)
+    segmentation_softmax = _softmax_for_export(segmentation_softmax, properties_dict, order, region_class_order, resampled_npz_fname,
+                                               force_separate_z, interpolation_order_z)
+    seg = resample_and_classify(segmentation_softmax, properties_dict, region_class_order, order, force_separate_z, interpolation_order_z)
+    _write_label_map(seg, out_fname, properties_dict)
+    return seg
+
+
+def save_segmentation_nifti_from_softmax(segmentation_softmax, out_fname, properties_dict, order=1, region_class_order=None,
+                                         seg_postprogess_fn=None, seg_postprocess_args=None, resampled_npz_fname=None,
+                                         non_postprocessed_fname=None, force_separate_z=None, interpolation_order_z=0, verbose=True):
+    """Same signature as the reference (segmentation_export.py:27-33).  Returns the uint8 array that is written.  Without a
+    `seg_postprogess_fn` the file is written from the device (`export_label_map_device`) and the array is copied back only to be
+    returned; with one, the label map goes to the host, through the function and through `utilities.nifti_io`'s host writer
+    (SimpleITK when it is installed) as before.  `resample_and_classify` is the device-only core for callers with their own writer."""
+    if seg_postprogess_fn is None:
+        return export_label_map_device(segmentation_softmax, out_fname, properties_dict, order, region_class_order, resampled_npz_fname,
+                                       force_separate_z, interpolation_order_z, verbose).cpu().numpy()
+    if verbose:
+        print("force_separate_z:", force_separate_z, "interpolation order:", order)
+    segmentation_softmax = _softmax_for_export(segmentation_softmax, properties_dict, order, region_class_order, resampled_npz_fname,
+                                               force_separate_z, interpolation_order_z)
     seg = resample_and_classify(segmentation_softmax, properties_dict, region_class_order, order, force_separate_z,
                                 interpolation_order_z).cpu().numpy()
-    post = seg_postprogess_fn(np.copy(seg), *seg_postprocess_args) if seg_postprogess_fn is not None else seg
-
-    def write(arr, fname):
-        write_image(arr.astype(np.uint8), fname, properties_dict['itk_spacing'], properties_dict['itk_origin'],
-                    properties_dict['itk_direction'])
-
-    write(post, out_fname)
-    if non_postprocessed_fname is not None and seg_postprogess_fn is not None:
-        write(seg, non_postprocessed_fname)
+    post = seg_postprogess_fn(np.copy(seg), *seg_postprocess_args)
+    _write_label_map(post, out_fname, properties_dict)
+    if non_postprocessed_fname is not None:
+        _write_label_map(seg, non_postprocessed_fname, properties_dict)
     return post

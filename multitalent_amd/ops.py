@@ -1319,5 +1319,65 @@ def patch_gather(sources, patch_size, pad_mode, data_out=None, seg_out=None, seg
     return data_out, seg_out
 
 
+_WRITE = "the gzip encoder of the label-map writer runs"
+DEFLATE_CHUNK = 65536
+_DEFLATE_HEAD = 1 << 20
+
+
+def deflate_gzip(payload, prefix=b'', chunk=DEFLATE_CHUNK, stages=None):
+    """payload: contiguous uint8 device tensor (any shape, any alignment); prefix: host bytes that precede it in the stream (at
+    most MT_DEFLATE_MAX_PREFIX, a file header).  -> bytes: one complete gzip member (mtime 0) of prefix + payload, a pure function
+    of the bytes and `chunk` (the size of the independently encoded pieces).  Two launches' worth of device work around one host
+    step: the symbol counts come back (316 words), utilities.deflate_host builds the code, the compressed bytes come back — with
+    the chunk CRCs in the same copy when they fit 1 MiB, so a label map costs one small and one final read-back.  See
+    mt_deflate_tokenize / mt_deflate_emit.  stages: a dict that receives the seconds spent in 'encode' and 'readback'."""
+    import time
+    from .utilities import deflate_host as H
+    _require_device(_WRITE, payload)
+    if payload.dtype != torch.uint8 or not payload.is_contiguous():
+        raise ValueError("deflate_gzip: a contiguous uint8 device tensor is expected, got %s" % payload.dtype)
+    prefix = bytes(prefix)
+    npay, npre, chunk = int(payload.numel()), len(prefix), int(chunk)
+    n = npay + npre
+    if n > H.MAX_INPUT:
+        raise ValueError("deflate_gzip: %d bytes; at most %d are encoded as one gzip member" % (n, H.MAX_INPUT))
+    lib = _lib.load()
+    t0 = time.perf_counter()
+    with torch.cuda.device(payload.device):
+        ws_bytes, out_bytes = int(lib.mt_deflate_workspace(n, chunk)), int(lib.mt_deflate_bound(n, chunk))
+        if not ws_bytes or npre > _lib.MT_DEFLATE_MAX_PREFIX:
+            raise ValueError("deflate_gzip: chunk of %d bytes or prefix of %d bytes outside the encoder's limits" % (chunk, npre))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=payload.device)
+        hist = torch.empty(H.LL_SYMBOLS + H.D_SYMBOLS, dtype=torch.int32, device=payload.device)
+        pre = (C.c_uint8 * max(npre, 1)).from_buffer_copy(prefix or b'\0')
+        _lib.check(lib.mt_deflate_tokenize(_ptr(payload), npay, pre, npre, chunk, _ptr(ws), ws_bytes, _ptr(hist), _stream()),
+                   'deflate_tokenize')
+        counts = hist.cpu().numpy().view(np.uint32)
+        _, _, hval, hbits, table = H.build_tables(counts[:H.LL_SYMBOLS].tolist(), counts[H.LL_SYMBOLS:].tolist())
+        header = np.frombuffer(hval.to_bytes(4 * ((hbits + 31) // 32), 'little'), dtype=np.uint32).copy()
+        out = torch.empty(out_bytes, dtype=torch.uint8, device=payload.device)
+        _lib.check(lib.mt_deflate_emit(_ptr(payload), npay, pre, npre, chunk, table.ctypes.data_as(C.c_void_p),
+                                       header.ctypes.data_as(C.c_void_p), hbits, _ptr(ws), ws_bytes, _ptr(out), out_bytes, _stream()),
+                   'deflate_emit')
+        if stages is not None:
+            torch.cuda.synchronize(payload.device)                  # (only when timed: the emit's device time counts as 'encode')
+        t1 = time.perf_counter()
+        nchunks = H.chunk_count(n, chunk)
+        data = 8 + (4 * nchunks + 7) // 8 * 8                       # out: int64 total, uint32 crc[nchunks], pad, stream
+        head = out[:min(out_bytes, data + _DEFLATE_HEAD)].cpu().numpy()
+        total = int(head[:8].view(np.int64)[0])
+        if not 0 <= total <= out_bytes - data:
+            raise RuntimeError("deflate_gzip: the device reported %d compressed bytes, the bound is %d" % (total, out_bytes - data))
+        crcs = head[8:8 + 4 * nchunks].view(np.uint32)
+        body = head[data:data + total].tobytes()
+        if data + total > head.size:                                # more than 1 MiB of compressed bytes: a second copy
+            body += out[head.size:data + total].cpu().numpy().tobytes()
+    crc = H.crc32_join(crcs, chunk, n - (nchunks - 1) * chunk)
+    if stages is not None:
+        stages['encode'] = stages.get('encode', 0.0) + (t1 - t0)
+        stages['readback'] = stages.get('readback', 0.0) + (time.perf_counter() - t1)
+    return H.gzip_member(body, crc, n)
+
+
 _parse_select_env()
 _select_env = _select

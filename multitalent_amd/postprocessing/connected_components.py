@@ -106,6 +106,10 @@ def load_remove_save(input_file, output_file, for_which_classes, minimum_valid_o
     img = read_image(input_file)
     img_npy = np.asarray(img.array)
     volume_per_voxel = float(np.prod(img.spacing, dtype=np.float64))
+    if img_npy.dtype == np.uint8 and img_npy.ndim == 3 and output_file.endswith('.nii.gz'):
+        # the label map stays on the device after the removal and is written from there (utilities.nifti_io.write_label_map_device)
+        ops.cc_check_shape(img_npy.shape)
+        img_npy = _to_device_uint8(img_npy)[0]
     image, largest_removed, kept_size = remove_all_but_the_largest_connected_component(img_npy, for_which_classes, volume_per_voxel,
                                                                                        minimum_valid_object_size)
     write_image(image, output_file, img.spacing, img.origin, img.direction)

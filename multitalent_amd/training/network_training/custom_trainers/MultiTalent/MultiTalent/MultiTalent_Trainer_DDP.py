@@ -200,7 +200,7 @@ class MultiTalent_trainer_ddp(nnUNetTrainerV2_DDP):
         import pickle
         from ......dataset_conversion.Task100_MultiTalent import MultiTalent_regions_class_order
         from ......evaluation.evaluator import aggregate_scores
-        from ......inference.segmentation_export import save_segmentation_nifti_from_softmax
+        from ......inference.segmentation_export import export_label_map_device
         current_mode = self.network.training
         self.network.eval()
         args = {'do_mirroring': do_mirroring, 'use_sliding_window': use_sliding_window, 'step_size': step_size,
@@ -234,14 +234,12 @@ class MultiTalent_trainer_ddp(nnUNetTrainerV2_DDP):
                                                   all_in_gpu)
             for r in MultiTalent_regions.keys():
                 ch = MultiTalent_region_output_idx_mapping[r]
-                save_segmentation_nifti_from_softmax(probs[ch:ch + 1], os.path.join(out_individual, fname + '__' + r + ".nii.gz"),
-                                                     properties, order, ((1,),), None, None, None, None, force_separate_z,
-                                                     order_z, verbose=False)
+                export_label_map_device(probs[ch:ch + 1], os.path.join(out_individual, fname + '__' + r + ".nii.gz"), properties, order,
+                                        ((1,),), None, force_separate_z, order_z)
             idx = [MultiTalent_region_output_idx_mapping[i] for i in MultiTalent_valid_regions[dataset_name]]
-            save_segmentation_nifti_from_softmax(probs[idx], os.path.join(out, fname + ".nii.gz"), properties, order,
-                                                 MultiTalent_regions_class_order[dataset_name], None, None,
-                                                 os.path.join(out, fname + ".npz") if save_softmax else None, None,
-                                                 force_separate_z, order_z, verbose=False)
+            export_label_map_device(probs[idx], os.path.join(out, fname + ".nii.gz"), properties, order,
+                                    MultiTalent_regions_class_order[dataset_name],
+                                    os.path.join(out, fname + ".npz") if save_softmax else None, force_separate_z, order_z)
         self._validation_barrier()
         self.print_to_log_file("finished prediction")
         if rank == 0 and self.gt_niftis_folder is not None and os.path.isdir(self.gt_niftis_folder):

@@ -444,7 +444,7 @@ class nnUNetTrainer(object):
         of the ground truth into `gt_niftis/` for a later consolidation across folds is not done."""
         import pickle
         from ...evaluation.evaluator import aggregate_scores
-        from ...inference.segmentation_export import save_segmentation_nifti_from_softmax
+        from ...inference.segmentation_export import export_label_map_device
         current_mode = self.network.training
         self.network.eval()
         args = {'do_mirroring': do_mirroring, 'use_sliding_window': use_sliding_window, 'step_size': step_size,
@@ -468,10 +468,8 @@ class nnUNetTrainer(object):
                     (save_softmax and not os.path.isfile(os.path.join(out, fname + ".npz"))):
                 probs = self._predict_validation_case(k, do_mirroring, mirror_axes, use_sliding_window, step_size, use_gaussian,
                                                       all_in_gpu)
-                save_segmentation_nifti_from_softmax(probs, os.path.join(out, fname + ".nii.gz"), properties, order,
-                                                     self.regions_class_order, None, None,
-                                                     os.path.join(out, fname + ".npz") if save_softmax else None, None,
-                                                     force_separate_z, order_z, verbose=False)
+                export_label_map_device(probs, os.path.join(out, fname + ".nii.gz"), properties, order, self.regions_class_order,
+                                        os.path.join(out, fname + ".npz") if save_softmax else None, force_separate_z, order_z)
         self._validation_barrier()
         self.print_to_log_file("finished prediction")
         if rank == 0 and self.gt_niftis_folder is not None and os.path.isdir(self.gt_niftis_folder):

@@ -5,7 +5,8 @@ SimpleITK is used when it is importable.  Otherwise `.nii` / `.nii.gz` files are
 codec below (single-file format, little endian, scalar volumes, sform or qform geometry): enough for CT volumes and label
 maps, nothing else.  Geometry follows ITK's conventions so that the `itk_*` properties of a case mean the same thing either
 way: arrays are indexed [z, y, x], spacing / origin are (x, y, z), the direction is the row-major 3x3 cosine matrix in LPS
-(NIfTI stores RAS: x and y are negated on the way in and out).  Host code, not part of the device path."""
+(NIfTI stores RAS: x and y are negated on the way in and out).  Host code, with one exception: a uint8 label map that is already
+on the device and goes to a `.nii.gz` is gzip-encoded there (`write_label_map_device`), behind the same header."""
 import gzip
 import struct
 
@@ -135,22 +136,19 @@ def _read_nifti(fname):
     return Image(arr, spacing, _LPS @ t, (_LPS @ Rras).ravel())
 
 
-def _write_nifti(img, fname):
-    arr = np.ascontiguousarray(img.array)
-    if arr.dtype == np.bool_:
-        arr = arr.astype(np.uint8)
-    if arr.dtype.name not in _CODES:
-        raise IOError("cannot write dtype %s as NIfTI" % arr.dtype)
-    arr = arr.astype(arr.dtype.newbyteorder('<'))
-    nz, ny, nx = arr.shape
-    sp = np.array(img.spacing, dtype=np.float64)
-    Rras = _LPS @ np.array(img.direction, dtype=np.float64).reshape(3, 3)
-    t = _LPS @ np.array(img.origin, dtype=np.float64)
+def _nifti_header(shape, dtype, spacing, origin, direction):
+    """-> the 348 header bytes + the 4 bytes of an empty extension: a single-file NIfTI-1 ('n+1') whose voxels follow at offset 352.
+    shape: [z, y, x] of the array, dtype: its numpy dtype; geometry in ITK's conventions (see the module text)."""
+    dtype = np.dtype(dtype)
+    nz, ny, nx = shape
+    sp = np.array(spacing, dtype=np.float64)
+    Rras = _LPS @ np.array(direction, dtype=np.float64).reshape(3, 3)
+    t = _LPS @ np.array(origin, dtype=np.float64)
     b, c, d, qfac = _matrix_to_quaternion(Rras)
     hdr = bytearray(348)
     struct.pack_into('<i', hdr, 0, 348)
     struct.pack_into('<8h', hdr, 40, 3, nx, ny, nz, 1, 1, 1, 1)
-    struct.pack_into('<hh', hdr, 70, _CODES[arr.dtype.name], arr.dtype.itemsize * 8)
+    struct.pack_into('<hh', hdr, 70, _CODES[dtype.name], dtype.itemsize * 8)
     struct.pack_into('<8f', hdr, 76, qfac, sp[0], sp[1], sp[2], 0, 0, 0, 0)
     struct.pack_into('<3f', hdr, 108, 352.0, 1.0, 0.0)
     hdr[123] = 2                                          # millimetres
@@ -160,13 +158,50 @@ def _write_nifti(img, fname):
     for r in range(3):
         struct.pack_into('<4f', hdr, 280 + 16 * r, M[r, 0], M[r, 1], M[r, 2], t[r])
     hdr[344:348] = b'n+1\0'
-    blob = bytes(hdr) + b'\0\0\0\0' + arr.tobytes()
+    return bytes(hdr) + b'\0\0\0\0'
+
+
+def _write_nifti(img, fname):
+    arr = np.ascontiguousarray(img.array)
+    if arr.dtype == np.bool_:
+        arr = arr.astype(np.uint8)
+    if arr.dtype.name not in _CODES:
+        raise IOError("cannot write dtype %s as NIfTI" % arr.dtype)
+    arr = arr.astype(arr.dtype.newbyteorder('<'))
+    blob = _nifti_header(arr.shape, arr.dtype, img.spacing, img.origin, img.direction) + arr.tobytes()
     if fname.endswith('.gz'):
         with gzip.open(fname, 'wb', compresslevel=1) as f:
             f.write(blob)
     else:
         with open(fname, 'wb') as f:
             f.write(blob)
+
+
+def _is_device_label_map(array, fname):
+    """a uint8 tensor on a HIP device, to be written as .nii.gz: the case the device encoder serves."""
+    if not fname.endswith('.nii.gz') or isinstance(array, np.ndarray):
+        return False
+    import torch
+    return torch.is_tensor(array) and array.is_cuda and array.dtype == torch.uint8 and array.dim() == 3
+
+
+def encode_label_map_device(array, spacing, origin, direction, stages=None):
+    """array: uint8 device tensor [z, y, x] -> the bytes of its .nii.gz file: `_nifti_header`'s 352 bytes travel as the encoder's
+    host prefix, the voxels are compressed where they are (ops.deflate_gzip) and only the compressed bytes reach the host."""
+    from .. import ops
+    header = _nifti_header(tuple(int(i) for i in array.shape), np.uint8, spacing, origin, direction)
+    return ops.deflate_gzip(array.contiguous(), header, stages=stages)
+
+
+def write_label_map_device(array, fname, spacing, origin, direction, stages=None):
+    """`encode_label_map_device` into the file `fname`; the host only appends bytes to a file."""
+    import time
+    member = encode_label_map_device(array, spacing, origin, direction, stages)
+    t0 = time.perf_counter()
+    with open(fname, 'wb') as f:
+        f.write(member)
+    if stages is not None:
+        stages['file'] = stages.get('file', 0.0) + (time.perf_counter() - t0)
 
 
 def read_image(fname):
@@ -179,6 +214,14 @@ def read_image(fname):
 
 
 def write_image(array, fname, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), direction=(1, 0, 0, 0, 1, 0, 0, 0, 1)):
+    """Host arrays: SimpleITK when it is installed, else `_write_nifti`.  A uint8 DEVICE tensor [z, y, x] written as .nii.gz is
+    compressed on the device (`write_label_map_device`), with `_write_nifti`'s header, whether or not SimpleITK is installed; any
+    other device tensor is refused (there is no silent copy to the host)."""
+    if _is_device_label_map(array, fname):
+        return write_label_map_device(array, fname, spacing, origin, direction)
+    if not isinstance(array, np.ndarray) and getattr(array, 'is_cuda', False):
+        raise TypeError("write_image: only a 3-D uint8 device tensor written as .nii.gz is encoded on the device; pass a host array "
+                        "for %s %s -> %s" % (getattr(array, 'dtype', '?'), tuple(getattr(array, 'shape', ())), fname))
     if _have_sitk():
         import SimpleITK as sitk
         im = sitk.GetImageFromArray(array)
