@@ -508,6 +508,24 @@ int mt_deflate_tokenize(const uint8_t* payload, long n_payload, const uint8_t* p
 int mt_deflate_emit(const uint8_t* payload, long n_payload, const uint8_t* prefix /* host */, int n_prefix, int chunk,
                     const uint64_t* table /* host, 513 */, const uint32_t* header /* host */, int header_bits,
                     void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes, mt_stream_t stream);
+/* The same encoder for payloads of multi-byte elements (stored float16 probabilities and float32 training cases in .npz members,
+ * where the reference calls np.savez_compressed) and for streams of more than one call.  Two more arguments:
+ * period (1, 2, 4 or 8; anything else is MT_EINVAL before any launch): position p of a chunk is IN A RUN when p - period lies in
+ *   the same chunk and byte[p] == byte[p - period].  A maximal stretch of L such positions is matches of (distance period, length
+ *   258) while 258 positions remain, then the remainder as one match when it is 3 or longer and as 1 or 2 literals otherwise; every
+ *   other position is a literal.  (Matches longer than their distance overlap, which DEFLATE allows.)  period 1 is the token stream
+ *   above.  The distance counter that is used is hist[286 + period - 1] for periods 1, 2 and 4 and hist[286 + 5] for period 8
+ *   (distance code 5 covers 7..8 with one extra bit, which the host puts into the table's match entries).
+ * final: 0 leaves BFINAL clear in the last chunk and byte-aligns it with the empty stored block like every other chunk, so that
+ *   the outputs of consecutive calls concatenate into one DEFLATE stream (each call with its own code table; the host joins the
+ *   CRCs).  That is how a member of more than INT32_MAX bytes is written.
+ * mt_deflate_tokenize / mt_deflate_emit are these with period = 1 and final = 1.  A lane packs its consecutive tokens in registers
+ * and stores whole words; only the first and last word of its bit range are shared with its neighbours and written with atomic OR. */
+int mt_deflate_tokenize_period(const uint8_t* payload, long n_payload, const uint8_t* prefix /* host */, int n_prefix, int chunk,
+                               int period, void* ws, size_t ws_bytes, uint32_t* hist /* device, 316 */, mt_stream_t stream);
+int mt_deflate_emit_period(const uint8_t* payload, long n_payload, const uint8_t* prefix /* host */, int n_prefix, int chunk,
+                           int period, int final, const uint64_t* table /* host, 513 */, const uint32_t* header /* host */,
+                           int header_bits, void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes, mt_stream_t stream);
 /* Connected-component post-processing (remove_all_but_the_largest_connected_component, postprocessing/connected_components.py:48-101).
  * mt_cc_label3d: `lmap, num_objects = scipy.ndimage.label(mask)` (:76) with scipy's default 3-D structure, 6-connectivity (face
  * neighbours only), on the mask {v : member[seg[v]] != 0} of a contiguous uint8 volume seg[D, H, W].  member: HOST array of 256

@@ -1,17 +1,21 @@
 // deflate.hip — a gzip / DEFLATE encoder for byte streams in device memory (label maps written as .nii.gz; the reference hands
-// the raw voxels to SimpleITK / Python's gzip on one host thread, segmentation_export.py:148-160).  The stream is a short HOST
-// prefix (the NIfTI header) followed by the device payload, cut into chunks that are encoded independently, one workgroup each:
-//   mt_deflate_tokenize  tokenises every chunk (run-length matches at distance 1), counts the 286 + 30 DEFLATE symbols of the whole
-//                        file and leaves each chunk's CRC-32 in the workspace;
+// the raw voxels to SimpleITK / Python's gzip on one host thread, segmentation_export.py:148-160; stored probabilities and training
+// cases written as .npz, where it calls np.savez_compressed).  The stream is a short HOST prefix (the NIfTI or .npy header) followed
+// by the device payload, cut into chunks that are encoded independently, one workgroup each:
+//   mt_deflate_tokenize  tokenises every chunk (run-length matches at distance `period`: 1, or the element size of the payload),
+//                        counts the 286 + 30 DEFLATE symbols of the whole call and leaves each chunk's CRC-32 in the workspace;
 //   (host)               builds ONE length-limited Huffman code from the counts, the dynamic-block header and the token table;
 //   mt_deflate_emit      sizes each chunk under that code, writes it as one dynamic block (or as stored blocks where those are
-//                        smaller) into the chunk's own zeroed region with atomicOr — tokens own disjoint bit ranges, so the bytes
-//                        do not depend on the order — and compacts the regions by the prefix sum of their byte counts.
-// Tokeniser and framing are restated in tests/deflate_host.py; the device output equals it byte for byte.
+//                        smaller) into the chunk's own zeroed region — a lane packs its consecutive tokens in registers and stores
+//                        whole words, only the first and last word of its bit range go through atomicOr; lanes own disjoint bit
+//                        ranges, so the bytes do not depend on the order — and compacts the regions by the prefix sum of their sizes.
+// Tokeniser and framing are restated in tests/deflate_host.py (period 1) and tests/deflate_period_host.py; the device output equals
+// them byte for byte.
 #include "stream_common.h"
 
 #define DF_THREADS 256
 #define DF_PER 16                                   // bytes per lane and tile: one ds_read_b128
+#define DF_BACK 8                                   // bytes a lane sees behind its own: the largest period
 #define DF_TILE (DF_THREADS * DF_PER)
 #define DF_NONE (-2147483647 - 1)
 #define DF_LL 286
@@ -21,6 +25,7 @@
 #define DF_TOK_SLOTS 513
 #define DF_HDR_WORDS 256                            // 8192 bits; a dynamic header has at most 14 + 3 + 19*3 + 316*14 = 4498
 #define DF_POLY 0xedb88320u
+#define DF_NOBYTE 256u                              // what stands for a byte in front of the chunk: equal to no byte
 
 // workspace: [prefix 512][token table 513 x 8, padded to 4608][header words 1024][crc u32 x nchunks][size i32 x nchunks][pad 16][regions]
 #define DF_WS_TAB MT_DEFLATE_MAX_PREFIX
@@ -33,6 +38,7 @@ static inline long df_region(int chunk) { return (df_stored_size(chunk) + 3) & ~
 static inline size_t df_ws_regions(long nchunks) { return ((size_t)DF_WS_CRC + 8 * (size_t)nchunks + 15) & ~(size_t)15; }
 static inline size_t df_out_data(long nchunks) { return 8 + (((size_t)nchunks * 4 + 7) & ~(size_t)7); }
 static inline bool df_args_ok(long n, int chunk) { return n >= 0 && n <= 2147483647l && chunk >= MT_DEFLATE_MIN_CHUNK && chunk <= MT_DEFLATE_MAX_CHUNK; }
+static inline bool df_period_ok(int period) { return period == 1 || period == 2 || period == 4 || period == 8; }
 
 struct DfShared {
   uint32_t w[DF_TILE / 4 + 4] __attribute__((aligned(16)));      // the tile as an aligned dword copy of global memory, + 1 byte of lookahead
@@ -109,7 +115,7 @@ __device__ __forceinline__ uint32_t df_reduce_xor(uint32_t v, int* red) {
   return x;
 }
 
-// nbits (<= 48) bits of v at bit position pos of a zeroed word array: tokens own disjoint bit ranges, OR is order independent
+// nbits (<= 48) bits of v at bit position pos of a zeroed word array: OR is order independent (header and end of block)
 __device__ __forceinline__ void df_put(uint32_t* out, uint32_t pos, uint64_t v) {
   const uint32_t wd = pos >> 5, sh = pos & 31;
   const uint32_t a = (uint32_t)(v << sh);
@@ -119,59 +125,105 @@ __device__ __forceinline__ void df_put(uint32_t* out, uint32_t pos, uint64_t v) 
   if (r >> 32) atomicOr(out + wd + 2, (uint32_t)(r >> 32));
 }
 
+// One lane's consecutive tokens, packed in a register pair and written a word at a time.  The lane owns the bits [pos, pos + its
+// bits) of a zeroed array and nobody else writes inside that range, so every word that lies wholly inside it is a plain store; the
+// word the range starts in (unless it starts on a word boundary) and the word it ends in are shared with the neighbours and go
+// through atomicOr.
+struct DfPack {
+  uint32_t* out; uint64_t acc; uint32_t wd, fill; bool shared;
+  __device__ __forceinline__ void open(uint32_t* o, uint32_t pos) { out = o; acc = 0; wd = pos >> 5; fill = pos & 31; shared = fill != 0; }
+  __device__ __forceinline__ void put32(uint32_t v, uint32_t nb) {     // nb <= 32 bits of v, fill <= 31 in front of them
+    acc |= (uint64_t)v << fill;
+    fill += nb;
+    if (fill >= 32) {
+      const uint32_t w = (uint32_t)acc;
+      if (shared) { if (w) atomicOr(out + wd, w); shared = false; } else out[wd] = w;
+      acc >>= 32; fill -= 32; ++wd;
+    }
+  }
+  __device__ __forceinline__ void put(uint64_t e) {                    // a token table entry: bits | nbits << 48
+    const uint32_t nb = (uint32_t)(e >> 48);
+    if (nb <= 32) put32((uint32_t)e, nb);
+    else { put32((uint32_t)e, 32); put32((uint32_t)(e >> 32) & 0xffffu, nb - 32); }
+  }
+  __device__ __forceinline__ void close() { if (fill && (uint32_t)acc) atomicOr(out + wd, (uint32_t)acc); }
+};
+
+// One lane's symbol counts: equal consecutive symbols (a literal-dense payload repeats its sign / exponent bytes, a run its
+// 258-matches) are added up in a register and reach the LDS histogram as one atomicAdd; the matches' distance symbol as one per lane.
+struct DfCount {
+  uint32_t* hist; int sym; uint32_t cnt, matches;
+  __device__ __forceinline__ void open(uint32_t* h) { hist = h; sym = 0; cnt = 0; matches = 0; }
+  __device__ __forceinline__ void add(int s, uint32_t k) {
+    if (s == sym) cnt += k;
+    else { if (cnt) atomicAdd(hist + sym, cnt); sym = s; cnt = k; }
+  }
+  __device__ __forceinline__ void close(int dsym) {
+    if (cnt) atomicAdd(hist + sym, cnt);
+    if (matches) atomicAdd(hist + DF_LL + dsym, matches);
+  }
+};
+
 enum { DF_MODE_HIST = 0, DF_MODE_COUNT = 1, DF_MODE_WRITE = 2 };
 
-// One lane's DF_PER positions p0 .. of a tile of m bytes.  by[0..15] are its bytes, by[16] the byte behind them, prevb the byte in
-// front (-1: none, the chunk starts here).  vs = tile position at which the run that reaches p0 started (negative: in an earlier
-// tile).  Position p of a run, at offset j from the run's start, emits
-//   j == 0: the literal;   j % 258 == 0: a match of 258;   else, at the run's last byte: a match of j % 258 when that is >= 3,
-//   else j % 258 literals
-// which is "first byte literal, then 258-matches while they fit, then the remainder" seen from where each token ENDS, so that
-// the tokens of a tile come out in stream order with no knowledge of the bytes behind the tile but one.
-template <int MODE>
-__device__ __forceinline__ uint32_t df_walk(const uint32_t (&by)[DF_PER + 1], int prevb, int p0, int m, bool chunk_ends, int vs,
+// One lane's DF_PER positions p0 .. of a tile of m bytes.  e[DF_BACK + i] is its byte i (i = DF_PER: the byte behind them),
+// e[DF_BACK - k] the byte k in front of them (DF_NOBYTE where the chunk has not begun).  Position p is IN A RUN when its byte equals
+// the one P in front of it.  vs = tile position of the last position in front of p0 that is not in a run (negative: in an earlier
+// tile).  Position p, at offset j from that start, emits
+//   j == 0: the literal;   j % 258 == 0: a match of 258;   else, at the stretch's last byte: a match of j % 258 when that is >= 3,
+//   else the j % 258 literals that end here
+// which is "literal, then 258-matches while they fit, then the remainder" seen from where each token ENDS, so that the tokens of
+// a tile come out in stream order with no knowledge of the bytes behind the tile but one.
+template <int MODE, int P>
+__device__ __forceinline__ uint32_t df_walk(const uint32_t (&e)[DF_BACK + DF_PER + 1], int p0, int m, bool chunk_ends, int vs,
                                              DfShared& S, uint32_t* out, uint32_t pos) {
   uint32_t bits = 0;
-  int jm = ((int)by[0] != prevb || p0 - 1 < vs) ? 0 : (p0 - 1 - vs) % 258;      // j % 258 of the position in front of p0
+  int jm = p0 - 1 < vs ? 0 : (p0 - 1 - vs) % 258;                     // j % 258 of the position in front of p0
+  DfPack pk; DfCount ct;
+  if (MODE == DF_MODE_WRITE) pk.open(out, pos);
+  if (MODE == DF_MODE_HIST) ct.open(S.hist);
 #pragma unroll
   for (int i = 0; i < DF_PER; ++i) {
     const int p = p0 + i;
     if (p < m) {
-      const uint32_t b = by[i];
-      const bool st = i == 0 ? (int)b != prevb : b != by[i - 1];
-      const bool en = (p == m - 1 && chunk_ends) || by[i + 1] != b;
+      const uint32_t b = e[DF_BACK + i];
+      const bool st = b != e[DF_BACK + i - P];
+      const bool en = (p == m - 1 && chunk_ends) || e[DF_BACK + i + 1] != e[DF_BACK + i + 1 - P];
       jm = st ? 0 : (jm == 257 ? 0 : jm + 1);
-      int tok = -1, rep = 1;
+      int tok = -1, lit2 = -1;                                         // lit2: a literal in front of tok (a remainder of 2)
       if (st) tok = (int)b;
       else if (jm == 0) tok = DF_TOK_MATCH0 + 255;
-      else if (en) { if (jm >= 3) tok = DF_TOK_MATCH0 + jm - 3; else { tok = (int)b; rep = jm; } }
+      else if (en) { if (jm >= 3) tok = DF_TOK_MATCH0 + jm - 3; else { tok = (int)b; if (jm == 2) lit2 = (int)e[DF_BACK + i - 1]; } }
       if (tok >= 0) {
         if (MODE == DF_MODE_HIST) {
-          if (tok < 256) atomicAdd(&S.hist[tok], (uint32_t)rep);
-          else { atomicAdd(&S.hist[df_length_symbol(tok - DF_TOK_MATCH0 + 3)], 1u); atomicAdd(&S.hist[DF_LL], 1u); }
+          if (lit2 >= 0) ct.add(lit2, 1u);
+          if (tok < 256) ct.add(tok, 1u);
+          else { ct.add(df_length_symbol(tok - DF_TOK_MATCH0 + 3), 1u); ++ct.matches; }
         } else {
-          const uint64_t e = S.tab[tok];
-          const uint32_t nb = (uint32_t)(e >> 48);
-          if (MODE == DF_MODE_WRITE) {
-            const uint64_t v = e & 0xffffffffffffull;
-            df_put(out, pos + bits, v);
-            if (rep == 2) df_put(out, pos + bits + nb, v);
+          const uint64_t t1 = S.tab[tok];
+          bits += (uint32_t)(t1 >> 48);
+          if (lit2 >= 0) {
+            const uint64_t t0 = S.tab[lit2];
+            bits += (uint32_t)(t0 >> 48);
+            if (MODE == DF_MODE_WRITE) pk.put(t0);
           }
-          bits += nb * rep;
+          if (MODE == DF_MODE_WRITE) pk.put(t1);
         }
       }
     }
   }
+  if (MODE == DF_MODE_WRITE) pk.close();
+  if (MODE == DF_MODE_HIST) ct.close(P == 8 ? 5 : P - 1);
   return bits;
 }
 
 // All tiles of one chunk [cs, cs + clen) of the stream.  HIST: counts into S.hist, returns the chunk's CRC-32.  COUNT: returns the
 // bits of the chunk's tokens.  WRITE: writes them from bit `bit0` of `out`.  The value is returned to every thread.
-template <int MODE>
-__device__ uint32_t df_sweep(const DfStream& X, long cs, int clen, DfShared& S, uint32_t* out, uint32_t bit0) {
+template <int MODE, int P>
+__device__ __forceinline__ uint32_t df_sweep(const DfStream& X, long cs, int clen, DfShared& S, uint32_t* out, uint32_t bit0) {
   const int t = threadIdx.x, p0 = t * DF_PER;
-  int carry = 0;                    // offset in its run of the tile's first byte, if that byte continues a run
-  int lastb = -1;                   // the byte in front of the tile
+  int carry = 0;                    // distance from the last position that is not in a run to the tile's first byte
+  uint64_t last8 = 0;               // the DF_BACK bytes in front of the tile, the nearest in the top byte
   uint32_t acc = MODE == DF_MODE_HIST ? 0xffffffffu : 0u;            // running CRC register / bit count
   for (int ts = 0; ts < clen; ts += DF_TILE) {
     const int m = clen - ts < DF_TILE ? clen - ts : DF_TILE;
@@ -199,8 +251,7 @@ __device__ uint32_t df_sweep(const DfStream& X, long cs, int clen, DfShared& S, 
       for (int k = t; k < L; k += DF_THREADS) ((uint8_t*)S.w)[k] = (uint8_t)X.byte(s + k);
     }
     __syncthreads();
-    uint32_t by[DF_PER + 1];
-    int prevb = lastb;
+    uint32_t e[DF_BACK + DF_PER + 1];
     {
       const uint4 q = ((const uint4*)S.w)[t];
       const uint32_t w4 = S.w[4 * t + 4];
@@ -210,32 +261,41 @@ __device__ uint32_t df_sweep(const DfStream& X, long cs, int clen, DfShared& S, 
       for (int k = 0; k < 4; ++k) al[k] = (uint32_t)((((uint64_t)wv[k + 1] << 32) | wv[k]) >> (8 * a));
       al[4] = w4 >> (8 * a);
 #pragma unroll
-      for (int i = 0; i <= DF_PER; ++i) by[i] = (al[i >> 2] >> (8 * (i & 3))) & 0xffu;
-      if (t > 0 && p0 < m) prevb = ((const uint8_t*)S.w)[a + p0 - 1];
+      for (int i = 0; i <= DF_PER; ++i) e[DF_BACK + i] = (al[i >> 2] >> (8 * (i & 3))) & 0xffu;
+      // the P bytes in front: from the two words in front of the lane's own, for lane 0 from the previous tile
+      uint64_t behind = last8;
+      if (t > 0) {
+        const uint64_t lo = ((uint64_t)S.w[4 * t - 1] << 32) | S.w[4 * t - 2];
+        behind = a ? (lo >> (8 * a)) | ((uint64_t)q.x << (64 - 8 * a)) : lo;
+      }
+      const int have = ts + p0;                                       // positions of the chunk in front of the lane
+#pragma unroll
+      for (int k = 1; k <= DF_BACK; ++k)
+        if (k <= P) e[DF_BACK - k] = k <= have ? (uint32_t)(behind >> (8 * (DF_BACK - k))) & 0xffu : DF_NOBYTE;
     }
-    // where the run that reaches this lane started: the last run start in an earlier lane of the tile, else the carry
+    // the last position in front of this lane that is not in a run: in an earlier lane of the tile, else the carry
     int ls = DF_NONE;
 #pragma unroll
     for (int i = 0; i < DF_PER; ++i)
-      if (p0 + i < m && (i == 0 ? (int)by[0] != prevb : by[i] != by[i - 1])) ls = p0 + i;
+      if (p0 + i < m && e[DF_BACK + i] != e[DF_BACK + i - P]) ls = p0 + i;
     int any;
     const int before = df_scan_max(ls, S.red, any);
     const int vs = before != DF_NONE ? before : -carry;
     if (MODE == DF_MODE_HIST) {
-      df_walk<DF_MODE_HIST>(by, prevb, p0, m, ends, vs, S, nullptr, 0);
+      df_walk<DF_MODE_HIST, P>(e, p0, m, ends, vs, S, nullptr, 0);
       // CRC: lane t's 16 bytes from a zero register (lane 0: from the running one), shifted past the full pieces behind it
       const int q = m >> 4, r = m & 15;
       uint32_t reg = t == 0 ? acc : 0u;                               // (with no full piece the register passes through)
       if (t < q) {
 #pragma unroll
-        for (int i = 0; i < DF_PER; ++i) reg = S.crctab[(reg ^ by[i]) & 0xffu] ^ (reg >> 8);
+        for (int i = 0; i < DF_PER; ++i) reg = S.crctab[(reg ^ e[DF_BACK + i]) & 0xffu] ^ (reg >> 8);
         reg = df_mulmod(reg, S.pow128[q - 1 - t]);
       }
       uint32_t x = df_reduce_xor(reg, S.red);
       if (r) {                                                        // the partial last piece continues from the joined register
         if (t == q) {
           uint32_t g = x;
-          for (int i = 0; i < r; ++i) g = S.crctab[(g ^ by[i]) & 0xffu] ^ (g >> 8);
+          for (int i = 0; i < r; ++i) g = S.crctab[(g ^ e[DF_BACK + i]) & 0xffu] ^ (g >> 8);
           S.red[4] = (int)g;
         }
         __syncthreads();
@@ -243,16 +303,20 @@ __device__ uint32_t df_sweep(const DfStream& X, long cs, int clen, DfShared& S, 
       }
       acc = x;
     } else if (MODE == DF_MODE_COUNT) {
-      acc += df_walk<DF_MODE_COUNT>(by, prevb, p0, m, ends, vs, S, nullptr, 0);
+      acc += df_walk<DF_MODE_COUNT, P>(e, p0, m, ends, vs, S, nullptr, 0);
     } else {
-      const uint32_t mine = df_walk<DF_MODE_COUNT>(by, prevb, p0, m, ends, vs, S, nullptr, 0);
+      const uint32_t mine = df_walk<DF_MODE_COUNT, P>(e, p0, m, ends, vs, S, nullptr, 0);
       uint32_t total;
       const uint32_t off = df_scan_sum(mine, S.red, total);
-      if (mine) df_walk<DF_MODE_WRITE>(by, prevb, p0, m, ends, vs, S, out, bit0 + acc + off);
+      if (mine) df_walk<DF_MODE_WRITE, P>(e, p0, m, ends, vs, S, out, bit0 + acc + off);
       acc += total;
     }
     carry = any != DF_NONE ? m - any : carry + m;
-    lastb = ((const uint8_t*)S.w)[a + m - 1];
+    if (!ends) {                                                      // (a tile that does not end the chunk is full)
+      last8 = 0;
+#pragma unroll
+      for (int k = 0; k < DF_BACK; ++k) last8 |= (uint64_t)((const uint8_t*)S.w)[a + m - DF_BACK + k] << (8 * k);
+    }
     __syncthreads();                                                  // the tile is overwritten next
   }
   if (MODE == DF_MODE_HIST) return ~acc;
@@ -264,6 +328,7 @@ __device__ uint32_t df_sweep(const DfStream& X, long cs, int clen, DfShared& S, 
   return 0;
 }
 
+template <int P>
 __global__ __launch_bounds__(DF_THREADS) void deflate_tokenize_kernel(DfStream X, int chunk, uint32_t* __restrict__ hist, uint32_t* __restrict__ crc) {
   __shared__ DfShared S;
   const int t = threadIdx.x;
@@ -284,7 +349,7 @@ __global__ __launch_bounds__(DF_THREADS) void deflate_tokenize_kernel(DfStream X
   __syncthreads();
   const long cs = (long)blockIdx.x * chunk;
   const int clen = (int)(X.n - cs < chunk ? X.n - cs : chunk);
-  const uint32_t c = df_sweep<DF_MODE_HIST>(X, cs, clen, S, nullptr, 0);
+  const uint32_t c = df_sweep<DF_MODE_HIST, P>(X, cs, clen, S, nullptr, 0);
   if (t == 0) { crc[blockIdx.x] = c; atomicAdd(&S.hist[256], 1u); }    // one end-of-block per chunk
   __syncthreads();
   for (int k = t; k < DF_HIST; k += DF_THREADS) if (S.hist[k]) atomicAdd(hist + k, S.hist[k]);
@@ -303,7 +368,8 @@ __device__ __forceinline__ uint32_t df_stored_byte(const DfStream& X, long cs, i
   return X.byte(cs + blk * 65535 + (r - 5));
 }
 
-__global__ __launch_bounds__(DF_THREADS) void deflate_emit_kernel(DfStream X, int chunk, long nchunks, const uint64_t* __restrict__ tab,
+template <int P>
+__global__ __launch_bounds__(DF_THREADS) void deflate_emit_kernel(DfStream X, int chunk, long nchunks, int ends_stream, const uint64_t* __restrict__ tab,
                                                                   const uint32_t* __restrict__ hdr, int hdr_bits, uint8_t* __restrict__ regions,
                                                                   long region, int32_t* __restrict__ sizes) {
   __shared__ DfShared S;
@@ -312,11 +378,11 @@ __global__ __launch_bounds__(DF_THREADS) void deflate_emit_kernel(DfStream X, in
   __syncthreads();
   const long c = blockIdx.x, cs = c * chunk;
   const int clen = (int)(X.n - cs < chunk ? X.n - cs : chunk);
-  const bool final = c == nchunks - 1;
+  const bool final = ends_stream && c == nchunks - 1;
   uint32_t* out = (uint32_t*)(regions + c * region);
-  const uint32_t tok_bits = df_sweep<DF_MODE_COUNT>(X, cs, clen, S, nullptr, 0);
+  const uint32_t tok_bits = df_sweep<DF_MODE_COUNT, P>(X, cs, clen, S, nullptr, 0);
   const uint64_t eob = S.tab[DF_TOK_EOB];
-  // BFINAL, header, tokens, end of block; every chunk but the last is closed by an empty stored block: 3 bits, pad, 00 00 ff ff
+  // BFINAL, header, tokens, end of block; every chunk but the stream's last is closed by an empty stored block: 3 bits, pad, 00 00 ff ff
   const long bits = 1 + (long)hdr_bits + tok_bits + (long)(eob >> 48) + (final ? 0 : 3);
   const long huff = ((bits + 7) >> 3) + (final ? 0 : 4);
   const long stored = df_stored_size(clen);
@@ -332,7 +398,7 @@ __global__ __launch_bounds__(DF_THREADS) void deflate_emit_kernel(DfStream X, in
   }
   if (t == 0 && final) atomicOr(out, 1u);
   for (int k = t; 32 * k < hdr_bits; k += DF_THREADS) df_put(out, 1 + 32 * k, hdr[k]);
-  df_sweep<DF_MODE_WRITE>(X, cs, clen, S, out, 1 + hdr_bits);
+  df_sweep<DF_MODE_WRITE, P>(X, cs, clen, S, out, 1 + hdr_bits);
   if (t == 0) {
     df_put(out, 1 + hdr_bits + tok_bits, eob & 0xffffffffffffull);
     if (!final) df_put(out, (uint32_t)(8 * (((bits + 7) >> 3) + 2)), 0xffffull);
@@ -374,11 +440,20 @@ extern "C" size_t mt_deflate_bound(long n, int chunk) {
   MT_REQUIRE(n_payload + n_prefix <= 2147483647l, who ": %ld bytes; at most INT32_MAX are encoded as one member", n_payload + n_prefix); \
   MT_REQUIRE(chunk >= MT_DEFLATE_MIN_CHUNK && chunk <= MT_DEFLATE_MAX_CHUNK, who ": chunk of %d bytes (%d .. %d)", chunk,            \
              MT_DEFLATE_MIN_CHUNK, MT_DEFLATE_MAX_CHUNK);                                                                             \
+  MT_REQUIRE(df_period_ok(period), who ": a period of %d bytes (1, 2, 4 or 8)", period);                                              \
   MT_REQUIRE(ws && (n_payload == 0 || payload) && (n_prefix == 0 || prefix), who ": NULL argument");                                  \
   MT_REQUIRE(((uintptr_t)ws & 15) == 0, who ": the workspace must be 16-byte aligned")
 
-extern "C" int mt_deflate_tokenize(const uint8_t* payload, long n_payload, const uint8_t* prefix, int n_prefix, int chunk,
-                                   void* ws, size_t ws_bytes, uint32_t* hist, mt_stream_t stream) {
+#define DF_LAUNCH_PERIOD(kernel, ...)                                                                      \
+  switch (period) {                                                                                        \
+    case 1: hipLaunchKernelGGL(kernel<1>, dim3((unsigned)nchunks), dim3(DF_THREADS), 0, s, __VA_ARGS__); break; \
+    case 2: hipLaunchKernelGGL(kernel<2>, dim3((unsigned)nchunks), dim3(DF_THREADS), 0, s, __VA_ARGS__); break; \
+    case 4: hipLaunchKernelGGL(kernel<4>, dim3((unsigned)nchunks), dim3(DF_THREADS), 0, s, __VA_ARGS__); break; \
+    default: hipLaunchKernelGGL(kernel<8>, dim3((unsigned)nchunks), dim3(DF_THREADS), 0, s, __VA_ARGS__); break; \
+  }
+
+extern "C" int mt_deflate_tokenize_period(const uint8_t* payload, long n_payload, const uint8_t* prefix, int n_prefix, int chunk, int period,
+                                          void* ws, size_t ws_bytes, uint32_t* hist, mt_stream_t stream) {
   DF_CHECK_ARGS("deflate_tokenize");
   MT_REQUIRE(hist, "deflate_tokenize: NULL argument");
   const long n = n_payload + n_prefix, nchunks = df_chunks(n, chunk);
@@ -391,14 +466,14 @@ extern "C" int mt_deflate_tokenize(const uint8_t* payload, long n_payload, const
     return MT_EHIP;
   }
   DfStream X; X.pre = w; X.pay = payload; X.npre = n_prefix; X.n = n;
-  hipLaunchKernelGGL(deflate_tokenize_kernel, dim3((unsigned)nchunks), dim3(DF_THREADS), 0, s, X, chunk, hist, (uint32_t*)(w + DF_WS_CRC));
+  DF_LAUNCH_PERIOD(deflate_tokenize_kernel, X, chunk, hist, (uint32_t*)(w + DF_WS_CRC));
   MT_CHECK_LAUNCH("deflate_tokenize");
   return MT_OK;
 }
 
-extern "C" int mt_deflate_emit(const uint8_t* payload, long n_payload, const uint8_t* prefix, int n_prefix, int chunk,
-                               const uint64_t* table, const uint32_t* header, int header_bits,
-                               void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes, mt_stream_t stream) {
+extern "C" int mt_deflate_emit_period(const uint8_t* payload, long n_payload, const uint8_t* prefix, int n_prefix, int chunk, int period,
+                                      int final, const uint64_t* table, const uint32_t* header, int header_bits,
+                                      void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes, mt_stream_t stream) {
   DF_CHECK_ARGS("deflate_emit");
   MT_REQUIRE(table && header && out, "deflate_emit: NULL argument");
   MT_REQUIRE(header_bits >= 17 && header_bits <= DF_HDR_WORDS * 32, "deflate_emit: a dynamic block header of %d bits", header_bits);
@@ -422,8 +497,8 @@ extern "C" int mt_deflate_emit(const uint8_t* payload, long n_payload, const uin
     return MT_EHIP;
   }
   DfStream X; X.pre = w; X.pay = payload; X.npre = n_prefix; X.n = n;
-  hipLaunchKernelGGL(deflate_emit_kernel, dim3((unsigned)nchunks), dim3(DF_THREADS), 0, s, X, chunk, nchunks, (const uint64_t*)(w + DF_WS_TAB),
-                     (const uint32_t*)(w + DF_WS_HDR), header_bits, regions, region, sizes);
+  DF_LAUNCH_PERIOD(deflate_emit_kernel, X, chunk, nchunks, final ? 1 : 0, (const uint64_t*)(w + DF_WS_TAB), (const uint32_t*)(w + DF_WS_HDR),
+                   header_bits, regions, region, sizes);
   MT_CHECK_LAUNCH("deflate_emit");
   hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(MT_SCAN_THREADS), 0, s, sizes, nchunks, (int64_t*)out);
   MT_CHECK_LAUNCH("deflate_emit (scan)");
@@ -431,4 +506,16 @@ extern "C" int mt_deflate_emit(const uint8_t* payload, long n_payload, const uin
                      df_out_data(nchunks));
   MT_CHECK_LAUNCH("deflate_emit (compact)");
   return MT_OK;
+}
+
+extern "C" int mt_deflate_tokenize(const uint8_t* payload, long n_payload, const uint8_t* prefix, int n_prefix, int chunk,
+                                   void* ws, size_t ws_bytes, uint32_t* hist, mt_stream_t stream) {
+  return mt_deflate_tokenize_period(payload, n_payload, prefix, n_prefix, chunk, 1, ws, ws_bytes, hist, stream);
+}
+
+extern "C" int mt_deflate_emit(const uint8_t* payload, long n_payload, const uint8_t* prefix, int n_prefix, int chunk,
+                               const uint64_t* table, const uint32_t* header, int header_bits,
+                               void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes, mt_stream_t stream) {
+  return mt_deflate_emit_period(payload, n_payload, prefix, n_prefix, chunk, 1, 1, table, header, header_bits, ws, ws_bytes, out, out_bytes,
+                                stream);
 }

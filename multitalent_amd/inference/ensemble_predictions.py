@@ -64,10 +64,12 @@ def upload_member(arr, device):
     return buf
 
 
-def merge_on_device(arrays, properties, regions_class_order=None, want_mean=False, device=None, keep_on_device=False):
+def merge_on_device(arrays, properties, regions_class_order=None, want_mean=False, device=None, keep_on_device=False,
+                    mean_on_device=False):
     """K float16 arrays [C, X, Y, Z] (X, Y, Z = size_after_cropping of `properties`) -> (uint8 label volume of
     `original_size_of_raw_data` as numpy — as a device tensor with `keep_on_device`, for the device file writer —, float16 mean
-    [C, X, Y, Z] as numpy or None)."""
+    [C, X, Y, Z] as numpy or None — with `mean_on_device` as a device tensor, a view of the padded rows the kernel wrote, for
+    utilities.npz_io.save_npz_device)."""
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("multitalent_amd: ensembling runs on a HIP device only; there is no CPU fallback")
@@ -92,6 +94,8 @@ def merge_on_device(arrays, properties, regions_class_order=None, want_mean=Fals
         assert order_t.numel() == C, "one class per channel expected in regions_class_order"
     mean = torch.empty((C, cs), dtype=torch.float16, device=device) if want_mean else None
     ensemble_classify(members, C, shape, cs, out, lo, order_t, mean, cs)
+    if want_mean and mean_on_device:
+        return (out if keep_on_device else out.cpu().numpy()), mean[:, :V].unflatten(1, shape)
     mean_np = mean[:, :V].cpu().numpy().reshape((C,) + shape) if want_mean else None
     return (out if keep_on_device else out.cpu().numpy()), mean_np
 
@@ -131,10 +135,12 @@ def merge_files(files, properties_files, out_file, override, store_npz, _loaded=
     from ..utilities.nifti_io import write_image
     if override or not os.path.isfile(out_file):
         arrays, props, regions_class_order = _loaded if _loaded is not None else _load_case(files, properties_files)
-        seg, mean = merge_on_device(arrays, props[0], regions_class_order, want_mean=store_npz, keep_on_device=out_file.endswith('.nii.gz'))
+        seg, mean = merge_on_device(arrays, props[0], regions_class_order, want_mean=store_npz, keep_on_device=out_file.endswith('.nii.gz'),
+                                    mean_on_device=True)
         write_image(seg, out_file, props[0]['itk_spacing'], props[0]['itk_origin'], props[0]['itk_direction'])
         if store_npz:
-            np.savez_compressed(out_file[:-7] + ".npz", softmax=mean)
+            from ..utilities.npz_io import save_npz_device
+            save_npz_device(out_file[:-7] + ".npz", softmax=mean)
             with open(out_file[:-7] + ".pkl", 'wb') as f:
                 pickle.dump(props, f)
 

@@ -142,7 +142,8 @@ def _softmax_for_export(segmentation_softmax, properties_dict, order, region_cla
         p = p.float()
         after = [int(i) for i in properties_dict.get('size_after_cropping')]
         sep = _separate_z_axis(properties_dict, force_separate_z) if any(i != j for i, j in zip(p.shape[1:], after)) else -1
-        np.savez_compressed(resampled_npz_fname, softmax=resample_softmax(p, after, sep).cpu().numpy().astype(np.float16))
+        from ..utilities.npz_io import save_npz_device
+        save_npz_device(resampled_npz_fname, softmax=resample_softmax(p, after, sep).half())     # compressed where it is
         if region_class_order is not None:
             properties_dict['regions_class_order'] = region_class_order
         with open(resampled_npz_fname[:-4] + ".pkl", 'wb') as f:

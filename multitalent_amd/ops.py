@@ -1331,34 +1331,56 @@ def deflate_gzip(payload, prefix=b'', chunk=DEFLATE_CHUNK, stages=None):
     step: the symbol counts come back (316 words), utilities.deflate_host builds the code, the compressed bytes come back — with
     the chunk CRCs in the same copy when they fit 1 MiB, so a label map costs one small and one final read-back.  See
     mt_deflate_tokenize / mt_deflate_emit.  stages: a dict that receives the seconds spent in 'encode' and 'readback'."""
-    import time
     from .utilities import deflate_host as H
     _require_device(_WRITE, payload)
     if payload.dtype != torch.uint8 or not payload.is_contiguous():
         raise ValueError("deflate_gzip: a contiguous uint8 device tensor is expected, got %s" % payload.dtype)
-    prefix = bytes(prefix)
-    npay, npre, chunk = int(payload.numel()), len(prefix), int(chunk)
+    body, crc, n = _deflate_call('deflate_gzip', payload, int(payload.numel()), bytes(prefix), int(chunk), None, True, stages)
+    return H.gzip_member(body, crc, n)
+
+
+def _deflate_alloc(nbytes, device):
+    """workspace and output of one encoder call (the tests put guard bytes around them here)"""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _deflate_call(who, payload, npay, prefix, chunk, period, final, stages):
+    """One tokenize / emit pair over prefix + the npay bytes at payload's address -> (raw DEFLATE bytes, CRC-32, stream bytes).
+    period None: the label-map entry points mt_deflate_tokenize / mt_deflate_emit (distance 1, final)."""
+    import time
+    from .utilities import deflate_host as H
+    npre = len(prefix)
     n = npay + npre
     if n > H.MAX_INPUT:
-        raise ValueError("deflate_gzip: %d bytes; at most %d are encoded as one gzip member" % (n, H.MAX_INPUT))
+        raise ValueError("%s: %d bytes; at most %d are encoded as one gzip member" % (who, n, H.MAX_INPUT))
+    if period is not None and period not in H.PERIODS:
+        raise ValueError("%s: a period of %r bytes; the encoder matches at a distance of 1, 2, 4 or 8" % (who, period))
     lib = _lib.load()
     t0 = time.perf_counter()
     with torch.cuda.device(payload.device):
         ws_bytes, out_bytes = int(lib.mt_deflate_workspace(n, chunk)), int(lib.mt_deflate_bound(n, chunk))
         if not ws_bytes or npre > _lib.MT_DEFLATE_MAX_PREFIX:
-            raise ValueError("deflate_gzip: chunk of %d bytes or prefix of %d bytes outside the encoder's limits" % (chunk, npre))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=payload.device)
+            raise ValueError("%s: chunk of %d bytes or prefix of %d bytes outside the encoder's limits" % (who, chunk, npre))
+        ws = _deflate_alloc(ws_bytes, payload.device)
         hist = torch.empty(H.LL_SYMBOLS + H.D_SYMBOLS, dtype=torch.int32, device=payload.device)
         pre = (C.c_uint8 * max(npre, 1)).from_buffer_copy(prefix or b'\0')
-        _lib.check(lib.mt_deflate_tokenize(_ptr(payload), npay, pre, npre, chunk, _ptr(ws), ws_bytes, _ptr(hist), _stream()),
-                   'deflate_tokenize')
+        if period is None:
+            _lib.check(lib.mt_deflate_tokenize(_ptr(payload), npay, pre, npre, chunk, _ptr(ws), ws_bytes, _ptr(hist), _stream()),
+                       'deflate_tokenize')
+        else:
+            _lib.check(lib.mt_deflate_tokenize_period(_ptr(payload), npay, pre, npre, chunk, period, _ptr(ws), ws_bytes, _ptr(hist),
+                                                      _stream()), 'deflate_tokenize_period')
         counts = hist.cpu().numpy().view(np.uint32)
-        _, _, hval, hbits, table = H.build_tables(counts[:H.LL_SYMBOLS].tolist(), counts[H.LL_SYMBOLS:].tolist())
+        _, _, hval, hbits, table = H.build_tables(counts[:H.LL_SYMBOLS].tolist(), counts[H.LL_SYMBOLS:].tolist(), period or 1)
         header = np.frombuffer(hval.to_bytes(4 * ((hbits + 31) // 32), 'little'), dtype=np.uint32).copy()
-        out = torch.empty(out_bytes, dtype=torch.uint8, device=payload.device)
-        _lib.check(lib.mt_deflate_emit(_ptr(payload), npay, pre, npre, chunk, table.ctypes.data_as(C.c_void_p),
-                                       header.ctypes.data_as(C.c_void_p), hbits, _ptr(ws), ws_bytes, _ptr(out), out_bytes, _stream()),
-                   'deflate_emit')
+        out = _deflate_alloc(out_bytes, payload.device)
+        tab_p, hdr_p = table.ctypes.data_as(C.c_void_p), header.ctypes.data_as(C.c_void_p)
+        if period is None:
+            _lib.check(lib.mt_deflate_emit(_ptr(payload), npay, pre, npre, chunk, tab_p, hdr_p, hbits, _ptr(ws), ws_bytes, _ptr(out),
+                                           out_bytes, _stream()), 'deflate_emit')
+        else:
+            _lib.check(lib.mt_deflate_emit_period(_ptr(payload), npay, pre, npre, chunk, period, 1 if final else 0, tab_p, hdr_p, hbits,
+                                                  _ptr(ws), ws_bytes, _ptr(out), out_bytes, _stream()), 'deflate_emit_period')
         if stages is not None:
             torch.cuda.synchronize(payload.device)                  # (only when timed: the emit's device time counts as 'encode')
         t1 = time.perf_counter()
@@ -1367,7 +1389,7 @@ def deflate_gzip(payload, prefix=b'', chunk=DEFLATE_CHUNK, stages=None):
         head = out[:min(out_bytes, data + _DEFLATE_HEAD)].cpu().numpy()
         total = int(head[:8].view(np.int64)[0])
         if not 0 <= total <= out_bytes - data:
-            raise RuntimeError("deflate_gzip: the device reported %d compressed bytes, the bound is %d" % (total, out_bytes - data))
+            raise RuntimeError("%s: the device reported %d compressed bytes, the bound is %d" % (who, total, out_bytes - data))
         crcs = head[8:8 + 4 * nchunks].view(np.uint32)
         body = head[data:data + total].tobytes()
         if data + total > head.size:                                # more than 1 MiB of compressed bytes: a second copy
@@ -1376,7 +1398,56 @@ def deflate_gzip(payload, prefix=b'', chunk=DEFLATE_CHUNK, stages=None):
     if stages is not None:
         stages['encode'] = stages.get('encode', 0.0) + (t1 - t0)
         stages['readback'] = stages.get('readback', 0.0) + (time.perf_counter() - t1)
-    return H.gzip_member(body, crc, n)
+    return body, crc, n
+
+
+DEFLATE_SEGMENT = 1 << 30
+
+
+def _payload_bytes(who, payload):
+    _require_device(_WRITE, payload)
+    if not payload.is_contiguous():
+        raise ValueError("%s: a contiguous device tensor is expected" % who)
+    return int(payload.numel()) * int(payload.element_size())
+
+
+def deflate_raw(payload, prefix=b'', chunk=DEFLATE_CHUNK, period=1, final=True, stages=None):
+    """payload: any contiguous device tensor, seen as its bytes in memory order (any alignment); prefix: host bytes in front of them.
+    -> (body, crc, n): the raw DEFLATE stream of prefix + payload with run-length matches at distance `period` (1, 2, 4 or 8: the
+    element size), the CRC-32 and the number of uncompressed bytes.  final=False leaves the stream open and byte-aligned, so that
+    the bodies of consecutive calls concatenate into one stream.  See mt_deflate_tokenize_period / mt_deflate_emit_period."""
+    npay = _payload_bytes('deflate_raw', payload)
+    return _deflate_call('deflate_raw', payload, npay, bytes(prefix), int(chunk), int(period), bool(final), stages)
+
+
+class deflate_segments(object):
+    """The raw DEFLATE stream of prefix + payload (as deflate_raw sees them) for a payload of any size, as a sequence of bodies: the
+    stream is cut into segments of `segment_bytes` (a multiple of the chunk in production; the prefix counts into the first), every
+    segment is one deflate_raw call with its own code table and only the last is final.  Iterate once; each body can be written
+    and dropped before the next is encoded.  Afterwards .crc (joined across the segments), .n and .compressed are set."""
+
+    def __init__(self, payload, prefix=b'', chunk=DEFLATE_CHUNK, period=1, segment_bytes=DEFLATE_SEGMENT, stages=None):
+        self.npay, self.prefix = _payload_bytes('deflate_segments', payload), bytes(prefix)
+        self.payload, self.chunk, self.period, self.segment, self.stages = payload, int(chunk), int(period), int(segment_bytes), stages
+        if not len(self.prefix) < self.segment <= DEFLATE_SEGMENT:
+            raise ValueError("deflate_segments: segments of %d bytes (more than the prefix, at most %d)" % (self.segment, DEFLATE_SEGMENT))
+        self.n, self.crc, self.compressed = self.npay + len(self.prefix), None, None
+
+    def __iter__(self):
+        from .utilities import deflate_host as H
+        flat = self.payload.reshape(-1).view(torch.uint8)
+        crc, done, compressed, pre = 0, 0, 0, self.prefix
+        while True:
+            take = min(self.segment - len(pre), self.npay - done)
+            last = done + take == self.npay
+            body, c, k = _deflate_call('deflate_segments', flat[done:done + take], take, pre, self.chunk, self.period, last, self.stages)
+            crc = H.crc32_combine(crc, c, k)
+            done, compressed, pre = done + take, compressed + len(body), b''
+            if last:
+                self.crc, self.compressed = crc, compressed
+            yield body
+            if last:
+                return
 
 
 _parse_select_env()

@@ -9,7 +9,7 @@
 
   ImageCropper          the static `crop` / `crop_from_list_of_files` of a single case, and the offline cropper of a dataset
                         (reference cropping.py:119-216): `run_cropping` writes `<case>.npz` / `<case>.pkl` and `gt_segmentations/`;
-                        `num_threads` host threads read the files and compress the results around the one device stream, and
+                        `num_threads` host threads read the files and write the results, which the device compresses, and
                         `properties['classes']` comes from `mt_label_presence`.
 
 There is no CPU labelling here: without a HIP device every function raises (the host path is `cropping.py`).  The data must be
@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..utilities.npz_io import encode_npz_device
 from .cropping import get_case_identifier, load_case_from_list_of_files  # noqa: F401  (same public names as cropping.py)
 
 
@@ -140,7 +141,8 @@ class ImageCropper(object):
     @staticmethod
     def _crop_loaded(data, seg, properties, case_identifier):
         """`crop` for the offline cropper: the same steps, with `properties['classes']` from `mt_label_presence` instead of a sort of
-        the volume.  -> all_data = vstack((data, seg)) as a host array, properties."""
+        the volume.  -> all_data = vstack((data, seg)) as a device tensor of numpy's result type (float32 data over an int64
+        mask is float64 there), properties."""
         data, seg, bbox = crop_to_nonzero(data, seg, nonzero_label=-1)
         properties["crop_bbox"] = bbox
         as_float = seg.dtype == torch.float32
@@ -148,10 +150,23 @@ class ImageCropper(object):
             labels = ops.label_presence(seg if as_float else seg.float(), "the segmentation of case %s" % case_identifier)
         properties['classes'] = np.array(labels, dtype=np.float32 if as_float else np.int64)          # np.unique(seg)
         properties["size_after_cropping"] = tuple(int(i) for i in data[0].shape)
-        return np.vstack((data.cpu().numpy(), seg.cpu().numpy())), properties
+        as_numpy = {torch.float32: np.float32, torch.float64: np.float64, torch.int64: np.int64, torch.int32: np.int32,
+                    torch.int16: np.int16, torch.uint8: np.uint8, torch.float16: np.float16}
+        both = np.result_type(as_numpy[data.dtype], as_numpy[seg.dtype])              # what np.vstack makes of the two
+        to = {v: k for k, v in as_numpy.items()}[both.type]
+        return torch.cat((data.to(to), seg.to(to)), 0), properties
 
     def _save(self, case_identifier, all_data, properties):
-        np.savez_compressed(os.path.join(self.output_folder, "%s.npz" % case_identifier), data=all_data)
+        """all_data: the device tensor (compressed on the device, utilities.npz_io), the members `encode_npz_device` made of it
+        (only the file is written here), or a host array (numpy's writer, as before)."""
+        from ..utilities import npz_io
+        fname = os.path.join(self.output_folder, "%s.npz" % case_identifier)
+        if isinstance(all_data, list):
+            npz_io.write_npz_members(fname, all_data)
+        elif torch.is_tensor(all_data) and all_data.is_cuda:
+            npz_io.save_npz_device(fname, data=all_data)
+        else:
+            np.savez_compressed(fname, data=all_data)
         self.save_properties(case_identifier, properties)
 
     def load_crop_save(self, case, case_identifier, overwrite_existing=False):
@@ -196,6 +211,7 @@ class ImageCropper(object):
                         nxt = todo[i + threads][0]
                         reads.append(pool.submit(load_case_from_list_of_files, nxt[:-1], nxt[-1]))
                     all_data, properties = self._crop_loaded(data, seg, properties, ident)
+                    all_data = encode_npz_device(data=all_data)                   # on this thread; the pool only writes the file
                 except Exception as e:
                     print("Exception in", ident, ":")
                     print(e)

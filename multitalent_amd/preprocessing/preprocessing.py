@@ -133,7 +133,16 @@ class GenericPreprocessor(object):
 
     @staticmethod
     def _save_case(output_folder_stage, case_identifier, all_data, properties):
-        np.savez_compressed(os.path.join(output_folder_stage, "%s.npz" % case_identifier), data=all_data)
+        """all_data: the float32 device tensor (compressed on the device, utilities.npz_io), the members `encode_npz_device` made
+        of it (only the file is written here), or a host array (numpy's writer, as before)."""
+        from ..utilities import npz_io
+        fname = os.path.join(output_folder_stage, "%s.npz" % case_identifier)
+        if isinstance(all_data, list):
+            npz_io.write_npz_members(fname, all_data)
+        elif torch.is_tensor(all_data) and all_data.is_cuda:
+            npz_io.save_npz_device(fname, data=all_data)
+        else:
+            np.savez_compressed(fname, data=all_data)
         with open(os.path.join(output_folder_stage, "%s.pkl" % case_identifier), 'wb') as f:
             pickle.dump(properties, f)
 
@@ -142,22 +151,24 @@ class GenericPreprocessor(object):
         self._run_case(target_spacing, case_identifier, output_folder_stage, cropped_output_dir, force_separate_z, all_classes, None)
 
     def _run_case(self, target_spacing, case_identifier, output_folder_stage, cropped_output_dir, force_separate_z, all_classes, writer):
-        """writer: None, or an executor that takes the compression and the file writes off this thread (`run`)."""
+        """writer: None, or an executor that takes the file writes off this thread (`run`); the case is compressed on the device,
+        from this thread, and only its compressed bytes wait for the executor."""
         if not torch.cuda.is_available():
             raise RuntimeError("multitalent_amd: training-case preprocessing runs on a HIP device only; there is no CPU fallback")
         data, seg, properties = self.load_cropped(cropped_output_dir, case_identifier)
         all_data, properties = self.preprocess_training_case(data, seg, properties, target_spacing, all_classes, force_separate_z)
-        all_data = all_data.cpu().numpy().astype(np.float32, copy=False)
+        all_data = all_data.float()
         print("saving: ", os.path.join(output_folder_stage, "%s.npz" % case_identifier))
         if writer is None:
             self._save_case(output_folder_stage, case_identifier, all_data, properties)
             return None
-        return writer.submit(self._save_case, output_folder_stage, case_identifier, all_data, properties)
+        from ..utilities.npz_io import encode_npz_device
+        return writer.submit(self._save_case, output_folder_stage, case_identifier, encode_npz_device(data=all_data), properties)
 
     def run(self, target_spacings, input_folder_with_cropped_npz, output_folder, data_identifier, num_threads=8, force_separate_z=None):
         """preprocessing.py:361-399: every cropped case of `input_folder_with_cropped_npz` into `<data_identifier>_stage<i>` per
         target spacing.  The cases go through the one device in sequence; `num_threads` (a number or one per stage) sizes the host
-        pool that compresses and writes the `.npz` files behind it."""
+        pool that writes the `.npz` files, which the device compresses, behind it."""
         if not torch.cuda.is_available():
             raise RuntimeError("multitalent_amd: training-case preprocessing runs on a HIP device only; there is no CPU fallback")
         print("Initializing to run preprocessing")

@@ -1,4 +1,5 @@
-"""Host side of the device gzip encoder (csrc/deflate.hip, ops.deflate_gzip): everything that is small and serial.
+"""Host side of the device gzip / DEFLATE encoder (csrc/deflate.hip, ops.deflate_gzip, ops.deflate_raw): everything that is small
+and serial.
 
 The device tokenises the byte stream and counts the DEFLATE symbols (286 literal/length + 30 distance counters); from those
 counts this module builds ONE length-limited Huffman code per file, the dynamic-block header that announces it and the table of
@@ -11,7 +12,7 @@ import numpy as np
 LL_SYMBOLS, D_SYMBOLS, EOB = 286, 30, 256
 MAX_BITS, MAX_CL_BITS = 15, 7
 MIN_MATCH, MAX_MATCH = 3, 258
-# index space of the token table: a literal byte b -> b, a match of length L at distance 1 -> 256 + (L - 3), end of block -> 512
+# index space of the token table: a literal byte b -> b, a match of length L at the call's one distance -> 256 + (L - 3), end of block -> 512
 TOKEN_MATCH0, TOKEN_EOB, TOKEN_SLOTS = 256, 512, 513
 CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
 GZIP_HEADER = b'\x1f\x8b\x08\x00\x00\x00\x00\x00\x00\xff'          # deflate, no flags, mtime 0, no extra flags, OS unknown
@@ -185,10 +186,21 @@ def dynamic_header(ll_lens, d_lens):
     return value, nbits
 
 
-def token_table(ll_lens, d_lens):
+PERIODS = (1, 2, 4, 8)
+
+
+def distance_symbol(period):
+    """the one match distance of a call -> (distance symbol, number of extra bits, extra value)  (RFC 1951 §3.2.5): distances 1..4
+    are the symbols 0..3, distance 8 is the upper half of symbol 5 (7..8, one extra bit)."""
+    if period not in PERIODS:
+        raise ValueError("the encoder matches at a distance of 1, 2, 4 or 8 bytes, not %r" % (period,))
+    return (5, 1, 1) if period == 8 else (period - 1, 0, 0)
+
+
+def token_table(ll_lens, d_lens, period=1):
     """-> uint64[TOKEN_SLOTS]: per token its bits (first bit in bit 0, Huffman codes already reversed, extra bits behind their code,
-    the distance-1 code behind a match) in the low 48 bits and their number in the bits above.  A token that does not occur has no
-    code and an entry of 0."""
+    the code of the distance `period` with its extra bit behind a match) in the low 48 bits and their number in the bits above.  A
+    token that does not occur has no code and an entry of 0."""
     ll_codes, d_codes = canonical_codes(ll_lens), canonical_codes(d_lens)
     tab = np.zeros(TOKEN_SLOTS, dtype=np.uint64)
 
@@ -198,8 +210,9 @@ def token_table(ll_lens, d_lens):
     for b in list(range(256)) + [EOB]:
         if ll_lens[b]:
             tab[TOKEN_EOB if b == EOB else b] = entry(_reverse(ll_codes[b], ll_lens[b]), ll_lens[b])
-    if d_lens[0]:
-        dist = (_reverse(d_codes[0], d_lens[0]), d_lens[0])
+    ds, deb, dev = distance_symbol(period)
+    if d_lens[ds]:
+        dist = (_reverse(d_codes[ds], d_lens[ds]) | (dev << d_lens[ds]), d_lens[ds] + deb)
         for length in range(MIN_MATCH, MAX_MATCH + 1):
             s, eb, ev = length_symbol(length)
             if ll_lens[s]:
@@ -212,12 +225,13 @@ def token_table(ll_lens, d_lens):
     return tab
 
 
-def build_tables(ll_hist, d_hist):
-    """the device's two histograms -> (ll_lens, d_lens, header value, header bits, token table)."""
+def build_tables(ll_hist, d_hist, period=1):
+    """the device's two histograms -> (ll_lens, d_lens, header value, header bits, token table); period: the match distance of
+    the call that counted them (mt_deflate_tokenize_period)."""
     ll_lens = code_lengths(ll_hist, MAX_BITS)
     d_lens = code_lengths(d_hist, MAX_BITS, at_least_two=False)
     value, nbits = dynamic_header(ll_lens, d_lens)
-    return ll_lens, d_lens, value, nbits, token_table(ll_lens, d_lens)
+    return ll_lens, d_lens, value, nbits, token_table(ll_lens, d_lens, period)
 
 
 # ---- CRC-32 (IEEE 802.3, reflected, polynomial 0xedb88320) of a concatenation from the CRCs of its parts ----
