@@ -315,6 +315,23 @@ int mt_lrelu_bwd_stats(float* g, const float* y, const float* scale, const float
                        const float* y2, const float* scale2, const float* shift2, float slope2, float* gcopy,
                        const float* mean, const float* rstd, float* part, int N, long V, int C, int gdtype /* of g, gcopy */,
                        int ydtype /* of y, y2 */, mt_stream_t stream);
+/* Which kernel instance a streaming launch takes (additions to ABI 4; the launch and the query read one decision).  The arguments are
+ * the launch's own, as far as the decision reads them; of a pointer only NULL-ness and alignment are read, so no memory needs to stand
+ * behind it, and no device is touched.  buf receives the name as a profiler prints it ("inorm_bwd_fast_kernel<2, true, 0, 0>",
+ * "inorm_bwd_small_kernel<8, 2, 1>", "inorm_apply_kernel": the strided kernels are no templates).  Returns what the launch would
+ * return for these arguments (MT_EINVAL where it refuses them).
+ * mt_inorm_lrelu_bwd_kernel_name names the kernel that writes dy; *own_reduce (may be NULL) = 1 when the launcher's own reduction pass
+ * over (g, y) runs before it (0 with external partials, and for the one-launch small kernel, which reduces in itself); *block (may be
+ * NULL) = threads per workgroup of the named kernel (256 .. 1024 for the small kernel). */
+int mt_inorm_lrelu_apply_kernel_name(const float* y, int ycs, const float* res, int rcs, const float* out, int ocs, int N, long V, int C,
+                                     int dtype, char* buf, size_t n);
+int mt_inorm_lrelu_bwd_kernel_name(const float* g, int gcs, const float* y, int ycs, const float* mean, const float* rstd, int N, long V, int C,
+                                   const float* part, int part_nblk, int part_cs, int part_c0, int gdtype, int ydtype,
+                                   char* buf, size_t n, int* own_reduce, int* block);
+int mt_lrelu_bwd_kernel_name(const float* g, int gcs, const float* y, int ycs, const float* y2, int y2cs, const float* gcopy, int gcopycs,
+                             int N, long V, int C, int gdtype, int ydtype, char* buf, size_t n);
+int mt_lrelu_bwd_stats_kernel_name(const float* g, const float* y, const float* y2, const float* gcopy, const float* mean, const float* rstd,
+                                   const float* part, int N, long V, int C, int gdtype, int ydtype, char* buf, size_t n);
 /* per-channel sum over all voxels: out[C] (+)= sum_{n,v} x[n,v,c]  (bias gradients of heads) */
 size_t mt_channel_sum_workspace(int N, long V, int C);
 int mt_channel_sum(const float* x, int xcs, int N, long V, int C, float* out, int accumulate,

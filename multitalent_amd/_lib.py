@@ -119,6 +119,10 @@ SIGNATURES = {
     'mt_lrelu_bwd': (_i, [_vp, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _vp, _vp, _f, _vp, _i, _i, _l, _i, _i, _i, _vp]),
     'mt_lrelu_bwd_stats_blocks': (_i, [_l, _i]),
     'mt_lrelu_bwd_stats': (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _l, _i, _i, _i, _vp]),
+    'mt_inorm_lrelu_apply_kernel_name': (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _l, _i, _i, C.c_char_p, _sz]),
+    'mt_inorm_lrelu_bwd_kernel_name': (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _l, _i, _vp, _i, _i, _i, _i, _i, C.c_char_p, _sz, _P(C.c_int), _P(C.c_int)]),
+    'mt_lrelu_bwd_kernel_name': (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _l, _i, _i, _i, C.c_char_p, _sz]),
+    'mt_lrelu_bwd_stats_kernel_name': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _i, _i, _i, C.c_char_p, _sz]),
     'mt_channel_sum_workspace': (_sz, [_i, _l, _i]),
     'mt_channel_sum': (_i, [_vp, _i, _i, _l, _i, _vp, _i, _vp, _sz, _i, _vp]),
     'mt_cast': (_i, [_vp, _i, _i, _vp, _i, _i, _l, _i, _i, _vp]),

@@ -129,15 +129,35 @@ __global__ __launch_bounds__(256) void inorm_apply_kernel(const ApplyParams P, i
   }
 }
 static int launch_apply_fast(const ApplyParams& P, int N, int dtype, int vec, mt_stream_t stream);
+// ---- dispatch of the launchers that choose between kernels (mt_inorm_lrelu_apply, mt_inorm_lrelu_bwd, mt_lrelu_bwd; mt_lrelu_bwd_stats
+// by storage pair): ONE decision per launch (*_resolve), read by the launch and by its mt_*_kernel_name query.  Only the NULL-ness and the alignment of a pointer are
+// read, so the queries may be asked with addresses nothing stands behind.
+// vec: elements per thread of the dense fast kernel, 0 = the strided kernel (inorm_apply_kernel)
+static int apply_resolve(const void* y, int ycs, const void* res, int rcs, const void* out, int ocs, int N, long V, int C, int dtype, int& vec) {
+  MT_REQUIRE(y && out && N > 0 && V > 0 && C > 0 && mt_dtype_ok(dtype), "inorm_lrelu_apply: bad args");
+  vec = 0;
+  if (ycs == C && ocs == C && (res == nullptr || rcs == C)) {
+    const int v = dense_vec(C, V * C, dtype, {y, out, res});
+    if (v > 0 && C / v <= 256) vec = v;
+  }
+  return MT_OK;
+}
+extern "C" int mt_inorm_lrelu_apply_kernel_name(const float* y, int ycs, const float* res, int rcs, const float* out, int ocs, int N, long V, int C,
+                                                int dtype, char* buf, size_t n) {
+  MT_REQUIRE(buf != nullptr && n > 0, "inorm_lrelu_apply_kernel_name: no buffer");
+  int vec;
+  if (int rc = apply_resolve(y, ycs, res, rcs, out, ocs, N, V, C, dtype, vec)) return rc;
+  if (vec > 0) snprintf(buf, n, "inorm_apply_fast_kernel<%d, %d>", vec, dtype);
+  else snprintf(buf, n, "inorm_apply_kernel");
+  return MT_OK;
+}
 extern "C" int mt_inorm_lrelu_apply(const float* y, int ycs, const float* scale, const float* shift, float slope,
                                     const float* res, int rcs, const float* rscale, const float* rshift, float rslope,
                                     float* out, int ocs, int N, long V, int C, int dtype, mt_stream_t stream) {
-  MT_REQUIRE(y && out && N > 0 && V > 0 && C > 0 && mt_dtype_ok(dtype), "inorm_lrelu_apply: bad args");
+  int vec;
+  if (int rc = apply_resolve(y, ycs, res, rcs, out, ocs, N, V, C, dtype, vec)) return rc;
   ApplyParams P{y, ycs, scale, shift, slope, res, rcs, rscale, rshift, rslope, out, ocs, V, C};
-  if (ycs == C && ocs == C && (res == nullptr || rcs == C)) {
-    const int vec = dense_vec(C, V * C, dtype, {y, out, res});
-    if (vec > 0 && C / vec <= 256) return launch_apply_fast(P, N, dtype, vec, stream);
-  }
+  if (vec > 0) return launch_apply_fast(P, N, dtype, vec, stream);
   hipLaunchKernelGGL(inorm_apply_kernel, dim3(nb_blocks(V), N), dim3(256), 0, (hipStream_t)stream, P, dtype);
   MT_CHECK_LAUNCH("inorm_lrelu_apply");
   return MT_OK;
@@ -494,12 +514,51 @@ static void inorm_bwd_fast_dispatch(const InBwdFast& F, dim3 grid, int vec, int 
     else launch_inorm_bwd_fast<2, MT_BF16, MT_BF16>(F, grid, reduce, st);
   }
 }
+enum { INB_GENERIC = 0, INB_FAST, INB_SMALL };
+struct InBwdChoice {
+  int form;      // the kernel that writes dy: inorm_bwd_apply_kernel | inorm_bwd_fast_kernel<vec, true, ..> | inorm_bwd_small_kernel<vec, ..>
+  int vec;       // elements per thread of the fast and the small form
+  int reduce;    // the launcher's own reduce pass runs (generic and fast form without external partials; the small form reduces in itself)
+  int block;     // threads per workgroup of the kernel that writes dy
+};
+static int inorm_bwd_resolve(const void* g, int gcs, const void* y, int ycs, const void* mean, const void* rstd, int N, long V, int C,
+                             const void* part, int part_nblk, int part_cs, int part_c0, int gdtype, int ydtype, InBwdChoice& c) {
+  MT_REQUIRE(g && y && mean && rstd && N > 0 && V > 0 && C > 0 && mt_dtype_ok(gdtype) && mt_dtype_ok(ydtype), "inorm_lrelu_bwd: bad args");
+  MT_REQUIRE(part == nullptr || (part_nblk > 0 && part_cs >= part_c0 + C && part_c0 >= 0), "inorm_lrelu_bwd: bad external partials");
+  // contiguous tensors take the vectorised lane-constant-channel path
+  const int vec = (gcs == C && ycs == C && ag_fast(ydtype, gdtype)) ? dense_vec(C, V * C, gdtype, {g, y}) : 0;
+  const bool contig = vec > 0 && (C / vec <= 256);
+  const int svec = gdtype == MT_F32 ? 4 : 8;
+  c.vec = contig ? vec : 0;
+  c.block = 256;
+  if (contig && part == nullptr && vec == svec && (long)N * V <= INORM_SMALL_MAX) {
+    c.form = INB_SMALL; c.reduce = 0;
+    c.block = V > 768 ? 1024 : V > 512 ? 768 : V > 256 ? 512 : 256;
+  } else {
+    c.form = contig ? INB_FAST : INB_GENERIC;
+    c.reduce = part == nullptr ? 1 : 0;
+  }
+  return MT_OK;
+}
+extern "C" int mt_inorm_lrelu_bwd_kernel_name(const float* g, int gcs, const float* y, int ycs, const float* mean, const float* rstd, int N, long V, int C,
+                                              const float* part, int part_nblk, int part_cs, int part_c0, int gdtype, int ydtype,
+                                              char* buf, size_t n, int* own_reduce, int* block) {
+  MT_REQUIRE(buf != nullptr && n > 0, "inorm_lrelu_bwd_kernel_name: no buffer");
+  InBwdChoice c;
+  if (int rc = inorm_bwd_resolve(g, gcs, y, ycs, mean, rstd, N, V, C, part, part_nblk, part_cs, part_c0, gdtype, ydtype, c)) return rc;
+  if (c.form == INB_SMALL) snprintf(buf, n, "inorm_bwd_small_kernel<%d, %d, %d>", c.vec, ydtype, gdtype);
+  else if (c.form == INB_FAST) snprintf(buf, n, "inorm_bwd_fast_kernel<%d, true, %d, %d>", c.vec, ydtype, gdtype);
+  else snprintf(buf, n, "inorm_bwd_apply_kernel");
+  if (own_reduce != nullptr) *own_reduce = c.reduce;
+  if (block != nullptr) *block = c.block;
+  return MT_OK;
+}
 extern "C" int mt_inorm_lrelu_bwd(float* g, int gcs, const float* y, int ycs, const float* mean, const float* rstd,
                                   const float* gamma, const float* beta, float slope, int N, long V, int C,
                                   float* dgamma, float* dbeta, float* dbias, const float* part, int part_nblk, int part_cs, int part_c0,
                                   void* ws, size_t ws_bytes, int gdtype, int ydtype, mt_stream_t stream) {
-  MT_REQUIRE(g && y && mean && rstd && N > 0 && V > 0 && C > 0 && mt_dtype_ok(gdtype) && mt_dtype_ok(ydtype), "inorm_lrelu_bwd: bad args");
-  MT_REQUIRE(part == nullptr || (part_nblk > 0 && part_cs >= part_c0 + C && part_c0 >= 0), "inorm_lrelu_bwd: bad external partials");
+  InBwdChoice ch;
+  if (int rc = inorm_bwd_resolve(g, gcs, y, ycs, mean, rstd, N, V, C, part, part_nblk, part_cs, part_c0, gdtype, ydtype, ch)) return rc;
   if (ws == nullptr || ws_bytes < mt_inorm_bwd_workspace(N, V, C)) { mt_set_error("inorm_lrelu_bwd: workspace too small"); return MT_EWORKSPACE; }
   InBwdParams P;
   P.g = g; P.gcs = gcs; P.y = y; P.ycs = ycs; P.mean = mean; P.rstd = rstd; P.gamma = gamma; P.beta = beta; P.slope = slope;
@@ -511,33 +570,30 @@ extern "C" int mt_inorm_lrelu_bwd(float* g, int gcs, const float* y, int ycs, co
   P.p1 = part ? part : P.part1; P.p1_nblk = part ? part_nblk : P.nvb; P.p1_cs = part ? part_cs : C; P.p1_c0 = part ? part_c0 : 0;
   P.gt = gdtype; P.at = ydtype;
   hipStream_t st = (hipStream_t)stream;
-  // contiguous tensors take the vectorised lane-constant-channel path
-  const int vec = (gcs == C && ycs == C && ag_fast(ydtype, gdtype)) ? dense_vec(C, V * C, gdtype, {g, y}) : 0;
-  const bool contig = vec > 0 && (C / vec <= 256);
-  const int svec = gdtype == MT_F32 ? 4 : 8;
-  if (contig && part == nullptr && vec == svec && (long)N * V <= INORM_SMALL_MAX) {
+  const int vec = ch.vec;
+  if (ch.form == INB_SMALL) {
     InBwdSmall S;
     S.g = g; S.y = y; S.mean = mean; S.rstd = rstd; S.gamma = gamma; S.beta = beta; S.slope = slope; S.V = V; S.C = C; S.N = N;
     S.dgamma = dgamma; S.dbeta = dbeta; S.dbias = dbias;
-    const dim3 grid(C / svec);
-    const dim3 blk(V > 768 ? 1024 : V > 512 ? 768 : V > 256 ? 512 : 256);
+    const dim3 grid(C / vec);
+    const dim3 blk(ch.block);
     if (gdtype == MT_F32) hipLaunchKernelGGL((inorm_bwd_small_kernel<4, MT_F32, MT_F32>), grid, blk, 0, st, S);
     else if (ydtype == MT_F16) hipLaunchKernelGGL((inorm_bwd_small_kernel<8, MT_F16, MT_BF16>), grid, blk, 0, st, S);
     else hipLaunchKernelGGL((inorm_bwd_small_kernel<8, MT_BF16, MT_BF16>), grid, blk, 0, st, S);
     MT_CHECK_LAUNCH("inorm_lrelu_bwd(small)");
     return MT_OK;
   }
-  if (contig) {
+  if (ch.form == INB_FAST) {
     InBwdFast F;
     F.g = g; F.y = y; F.mean = mean; F.rstd = rstd; F.gamma = gamma; F.beta = beta; F.slope = slope;
     F.nvec = (long)V * C / vec; F.C = C; F.G = C / vec; F.A = (256 / F.G) * F.G; F.nblk = P.nvb;
     F.part1 = P.part1; F.m = P.m; F.part2 = P.part2;
     dim3 grid(P.nvb, N);
-    if (part == nullptr) inorm_bwd_fast_dispatch(F, grid, vec, ydtype, gdtype, true, st);   // (the first pass was not fused into the kernel that produced g)
+    if (ch.reduce) inorm_bwd_fast_dispatch(F, grid, vec, ydtype, gdtype, true, st);   // (the first pass was not fused into the kernel that produced g)
     hipLaunchKernelGGL(inorm_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, P, N, dgamma, dbeta);
     inorm_bwd_fast_dispatch(F, grid, vec, ydtype, gdtype, false, st);
   } else {
-    if (part == nullptr) hipLaunchKernelGGL(inorm_bwd_reduce_kernel, dim3(P.nvb, N), dim3(256), 0, st, P);
+    if (ch.reduce) hipLaunchKernelGGL(inorm_bwd_reduce_kernel, dim3(P.nvb, N), dim3(256), 0, st, P);
     hipLaunchKernelGGL(inorm_bwd_finalize_kernel, dim3(C), dim3(256), 0, st, P, N, dgamma, dbeta);
     hipLaunchKernelGGL(inorm_bwd_apply_kernel, dim3(P.nvb, N), dim3(256), 0, st, P);
   }
@@ -712,19 +768,37 @@ static void launch_lrelu_bwd_fast(const LBwdParams& P, dim3 grid, int vec, const
   }
 }
 
+// vec: elements per thread of lrelu_bwd_fast_kernel, 0 = the strided kernel (lrelu_bwd_kernel)
+static int lrelu_bwd_resolve(const void* g, int gcs, const void* y, int ycs, const void* y2, int y2cs, const void* gcopy, int gcopycs, int N, long V,
+                             int C, int gdtype, int ydtype, int& vec) {
+  MT_REQUIRE(g && y && N > 0 && V > 0 && C > 0 && mt_dtype_ok(gdtype) && mt_dtype_ok(ydtype), "lrelu_bwd: bad args");
+  vec = 0;
+  if (gcs == C && ycs == C && (y2 == nullptr || y2cs == C) && (gcopy == nullptr || gcopycs == C) && V * C < (1L << 40) && ag_fast(ydtype, gdtype)) {
+    const int v = dense_vec(C, V * C, gdtype, {g, y, y2, gcopy});
+    if (v > 0 && C / v <= 256) vec = v;
+  }
+  return MT_OK;
+}
+extern "C" int mt_lrelu_bwd_kernel_name(const float* g, int gcs, const float* y, int ycs, const float* y2, int y2cs, const float* gcopy, int gcopycs,
+                                        int N, long V, int C, int gdtype, int ydtype, char* buf, size_t n) {
+  MT_REQUIRE(buf != nullptr && n > 0, "lrelu_bwd_kernel_name: no buffer");
+  int vec;
+  if (int rc = lrelu_bwd_resolve(g, gcs, y, ycs, y2, y2cs, gcopy, gcopycs, N, V, C, gdtype, ydtype, vec)) return rc;
+  if (vec > 0) snprintf(buf, n, "lrelu_bwd_fast_kernel<%d, %d, %d>", vec, ydtype, gdtype);
+  else snprintf(buf, n, "lrelu_bwd_kernel");
+  return MT_OK;
+}
 extern "C" int mt_lrelu_bwd(float* g, int gcs, const float* y, int ycs, const float* scale, const float* shift, float slope,
                             const float* y2, int y2cs, const float* scale2, const float* shift2, float slope2,
                             float* gcopy, int gcopycs, int N, long V, int C, int gdtype, int ydtype, mt_stream_t stream) {
-  MT_REQUIRE(g && y && N > 0 && V > 0 && C > 0 && mt_dtype_ok(gdtype) && mt_dtype_ok(ydtype), "lrelu_bwd: bad args");
+  int vec;
+  if (int rc = lrelu_bwd_resolve(g, gcs, y, ycs, y2, y2cs, gcopy, gcopycs, N, V, C, gdtype, ydtype, vec)) return rc;
   LBwdParams P{g, gcs, y, ycs, scale, shift, slope, y2, y2cs, scale2, shift2, slope2, gcopy, gcopycs, V, C, gdtype, ydtype};
-  if (gcs == C && ycs == C && (y2 == nullptr || y2cs == C) && (gcopy == nullptr || gcopycs == C) && V * C < (1L << 40) && ag_fast(ydtype, gdtype)) {
-    const int vec = dense_vec(C, V * C, gdtype, {g, y, y2, gcopy});
-    if (vec > 0 && C / vec <= 256) {
-      const DenseGeo geo = dense_geo(V, C, vec);
-      MT_AG_SWITCH(ydtype, gdtype, (launch_lrelu_bwd_fast<AT, GT>(P, dim3(geo.nblk, N), vec, geo, (hipStream_t)stream)), (void)0);
-      MT_CHECK_LAUNCH("lrelu_bwd_fast");
-      return MT_OK;
-    }
+  if (vec > 0) {
+    const DenseGeo geo = dense_geo(V, C, vec);
+    MT_AG_SWITCH(ydtype, gdtype, (launch_lrelu_bwd_fast<AT, GT>(P, dim3(geo.nblk, N), vec, geo, (hipStream_t)stream)), (void)0);
+    MT_CHECK_LAUNCH("lrelu_bwd_fast");
+    return MT_OK;
   }
   hipLaunchKernelGGL(lrelu_bwd_kernel, dim3(nb_blocks(V), N), dim3(256), 0, (hipStream_t)stream, P);
   MT_CHECK_LAUNCH("lrelu_bwd");
@@ -819,13 +893,28 @@ extern "C" int mt_lrelu_bwd_stats_blocks(long V, int C) {
   if (V <= 0 || C <= 0 || (C % 4) != 0 || C / 4 > 256 || (((long)V * C * 4) % 16) != 0) return 0;
   return nb_blocks(V);
 }
+// one instance per storage pair (lrelu_bwd_stats_kernel<4, AT, GT>); what the launch refuses, the name query refuses with the same code
+static int lrelu_bwd_stats_resolve(const void* g, const void* y, const void* y2, const void* gcopy, const void* mean, const void* rstd, const void* part,
+                                   int N, long V, int C, int gdtype, int ydtype, int& nblk) {
+  MT_REQUIRE(g && y && mean && rstd && part && N > 0 && ag_fast(ydtype, gdtype), "lrelu_bwd_stats: storage types (g %d, y %d) not taken (fp32/fp32, bf16/fp16, bf16/bf16)", gdtype, ydtype);
+  nblk = mt_lrelu_bwd_stats_blocks(V, C);
+  MT_REQUIRE(nblk > 0, "lrelu_bwd_stats: unsupported shape (V=%ld, C=%d): ask mt_lrelu_bwd_stats_blocks", V, C);
+  MT_REQUIRE(((((uintptr_t)g) | ((uintptr_t)y) | ((uintptr_t)y2) | ((uintptr_t)gcopy)) & 15) == 0, "lrelu_bwd_stats: tensors must be 16-byte aligned");
+  return MT_OK;
+}
+extern "C" int mt_lrelu_bwd_stats_kernel_name(const float* g, const float* y, const float* y2, const float* gcopy, const float* mean, const float* rstd,
+                                              const float* part, int N, long V, int C, int gdtype, int ydtype, char* buf, size_t n) {
+  MT_REQUIRE(buf != nullptr && n > 0, "lrelu_bwd_stats_kernel_name: no buffer");
+  int nblk;
+  if (int rc = lrelu_bwd_stats_resolve(g, y, y2, gcopy, mean, rstd, part, N, V, C, gdtype, ydtype, nblk)) return rc;
+  snprintf(buf, n, "lrelu_bwd_stats_kernel<4, %d, %d>", ydtype, gdtype);
+  return MT_OK;
+}
 extern "C" int mt_lrelu_bwd_stats(float* g, const float* y, const float* scale, const float* shift, float slope,
                                   const float* y2, const float* scale2, const float* shift2, float slope2, float* gcopy,
                                   const float* mean, const float* rstd, float* part, int N, long V, int C, int gdtype, int ydtype, mt_stream_t stream) {
-  MT_REQUIRE(g && y && mean && rstd && part && N > 0 && ag_fast(ydtype, gdtype), "lrelu_bwd_stats: storage types (g %d, y %d) not taken (fp32/fp32, bf16/fp16, bf16/bf16)", gdtype, ydtype);
-  const int nblk = mt_lrelu_bwd_stats_blocks(V, C);
-  MT_REQUIRE(nblk > 0, "lrelu_bwd_stats: unsupported shape (V=%ld, C=%d): ask mt_lrelu_bwd_stats_blocks", V, C);
-  MT_REQUIRE(((((uintptr_t)g) | ((uintptr_t)y) | ((uintptr_t)y2) | ((uintptr_t)gcopy)) & 15) == 0, "lrelu_bwd_stats: tensors must be 16-byte aligned");
+  int nblk;
+  if (int rc = lrelu_bwd_stats_resolve(g, y, y2, gcopy, mean, rstd, part, N, V, C, gdtype, ydtype, nblk)) return rc;
   LBwdStats P;
   P.g = g; P.y = y; P.y2 = y2; P.gcopy = gcopy; P.scale = scale; P.shift = shift; P.slope = slope;
   P.scale2 = scale2; P.shift2 = shift2; P.slope2 = slope2; P.mean = mean; P.rstd = rstd;

@@ -517,6 +517,43 @@ def inorm_lrelu_bwd(g, y, gamma, beta, dgamma, dbeta, dbias, ws, part=None, part
         'inorm_lrelu_bwd')
 
 
+def _addr(a):
+    return C.c_void_p(int(a)) if a else C.c_void_p(0)
+
+
+def inorm_lrelu_apply_kernel_name(y, ycs, res, rcs, out, ocs, N, V, Cn, dt):
+    """The kernel instance mt_inorm_lrelu_apply launches.  y / res / out: ADDRESSES (int, 0 or None = NULL; only NULL-ness and alignment
+    are read, nothing needs to stand behind them), dt: storage type code.  Same for the three queries below."""
+    buf = C.create_string_buffer(128)
+    _lib.check(_lib.load().mt_inorm_lrelu_apply_kernel_name(_addr(y), ycs, _addr(res), rcs, _addr(out), ocs, N, V, Cn, dt, buf, 128),
+               'inorm_lrelu_apply_kernel_name')
+    return buf.value.decode()
+
+
+def inorm_lrelu_bwd_kernel_name(g, gcs, y, ycs, N, V, Cn, gdt, ydt, part=0, part_nblk=0, part_cs=0, part_c0=0, mean=64, rstd=64):
+    """(name of the kernel that writes dy, whether the launcher's own reduction pass runs, threads per workgroup of the named kernel)"""
+    buf = C.create_string_buffer(128)
+    red, blk = C.c_int(-1), C.c_int(-1)
+    _lib.check(_lib.load().mt_inorm_lrelu_bwd_kernel_name(_addr(g), gcs, _addr(y), ycs, _addr(mean), _addr(rstd), N, V, Cn, _addr(part), part_nblk,
+                                                          part_cs, part_c0, gdt, ydt, buf, 128, C.byref(red), C.byref(blk)),
+               'inorm_lrelu_bwd_kernel_name')
+    return buf.value.decode(), bool(red.value), blk.value
+
+
+def lrelu_bwd_kernel_name(g, gcs, y, ycs, y2, y2cs, gcopy, gcopycs, N, V, Cn, gdt, ydt):
+    buf = C.create_string_buffer(128)
+    _lib.check(_lib.load().mt_lrelu_bwd_kernel_name(_addr(g), gcs, _addr(y), ycs, _addr(y2), y2cs, _addr(gcopy), gcopycs, N, V, Cn, gdt, ydt,
+                                                    buf, 128), 'lrelu_bwd_kernel_name')
+    return buf.value.decode()
+
+
+def lrelu_bwd_stats_kernel_name(g, y, y2, gcopy, N, V, Cn, gdt, ydt, mean=64, rstd=64, part=64):
+    buf = C.create_string_buffer(128)
+    _lib.check(_lib.load().mt_lrelu_bwd_stats_kernel_name(_addr(g), _addr(y), _addr(y2), _addr(gcopy), _addr(mean), _addr(rstd), _addr(part),
+                                                          N, V, Cn, gdt, ydt, buf, 128), 'lrelu_bwd_stats_kernel_name')
+    return buf.value.decode()
+
+
 def conv_bwd_stats_supported(p):
     return bool(_lib.load().mt_conv3d_bwd_stats_supported(C.byref(p)))
 

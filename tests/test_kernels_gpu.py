@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from stream_cases import relerr          # max |a - b| / max |b| in float64 (shared with tests/test_stream_kernels_gpu.py)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -26,10 +28,6 @@ def _bf16_round(x):
     from oracle.reference_ops import bf16_round
     return bf16_round(x)
 
-
-def relerr(a, b):
-    a, b = a.double(), b.double()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-12))
 
 
 def run_conv(dev, srcs_cpu, w, b, stride, pad, lazy=None, stats=False):

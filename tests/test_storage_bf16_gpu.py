@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from stream_cases import close_16bit          # the 16-bit apply rule (shared with tests/test_stream_kernels_gpu.py)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -88,9 +90,7 @@ def test_streaming_kernels_16bit(dev, C, shape, adt):
     ops.inorm_lrelu_apply(ops.Act(y, scale=sc, shift=sh, slope=0.01), ops.Act(out), res=ops.Act(r, scale=rsc, shift=rsh, slope=1.0))
     t = torch.addcmul(bc(sh), y.float(), bc(sc))        # fma
     ref = lre(t + lre(torch.addcmul(bc(rsh), r.float(), bc(rsc)), 1.0), 0.01)
-    d = (out.float() - rbf(ref, adt)).abs().max()
-    assert float(d) <= float(ref.abs().max()) * ulp, float(d)         # at most one ulp (fma vs mul+add before the rounding)
-    assert float((out.float() != rbf(ref, adt)).float().mean()) < 0.01
+    close_16bit(out, ref, ADT)          # at most one ulp of the maximum (fma vs mul+add before the rounding), < 1 % of the elements differ
     # ---- norm backward
     mean = y.float().mean((1, 2, 3))
     var = y.float().var((1, 2, 3), unbiased=False)
