@@ -543,6 +543,39 @@ int mt_deflate_tokenize_period(const uint8_t* payload, long n_payload, const uin
 int mt_deflate_emit_period(const uint8_t* payload, long n_payload, const uint8_t* prefix /* host */, int n_prefix, int chunk,
                            int period, int final, const uint64_t* table /* host, 513 */, const uint32_t* header /* host */,
                            int header_bits, void* ws, size_t ws_bytes, uint8_t* out, size_t out_bytes, mt_stream_t stream);
+/* Reader of the same files: INFLATE (RFC 1951: stored, fixed and dynamic blocks, every length and distance code) of a raw DEFLATE
+ * stream comp[0, n_comp) in DEVICE memory (any alignment, 1 .. INT32_MAX - 64 bytes), parallel over the stream's byte-aligned
+ * restart points.  A UNIT starts at a byte position, decodes consecutive blocks and ends behind an EMPTY stored block (3 bits,
+ * padding, 00 00 ff ff: what mt_deflate_emit puts behind every Huffman-coded chunk and zlib's Z_FULL_FLUSH behind its data; the
+ * next unit starts at the following byte) or at a block with BFINAL.  Non-empty stored blocks belong to the unit they occur in.
+ * mt_inflate_scan: candidates are position 0 and every position behind an occurrence of 00 00 ff ff, in order; more than
+ *   n_comp / 5 + 2 of them (true units are at least 5 bytes long) is status FOREIGN.  Every candidate is decoded without output by
+ *   one wave: a read behind the input, an invalid block, an over-subscribed code, an unassigned code or a match that reaches in
+ *   front of its unit make it BAD, more than unit_limit (1 .. 2^30) bytes from Huffman-coded blocks TOO_LONG.  One wave then
+ *   follows end -> start from position 0: every end must be a candidate; a candidate on the way that failed gives its status to the
+ *   stream, an end that is no candidate, or a chain that does not end at n_comp with BFINAL (final != 0) / at n_comp with or
+ *   without it (final == 0: the body of mt_deflate_emit_period with final = 0), gives CORRUPT.  Candidates that are not reached
+ *   are ignored, whatever they decoded to.  n_expect >= 0 and a different total gives SIZE.
+ *   ws (DEVICE, 16-byte aligned, mt_inflate_workspace(n_comp) bytes) begins with { int32 status; int32 n_units; int64 total;
+ *   int32 n_cand; int32 n_spans; }: status 0 OK, 1 FOREIGN, 2 TOO_LONG, 3 BAD, 4 CORRUPT, 5 SIZE; behind it the candidates,
+ *   their results and the chain (start, output offset as a 64-bit exclusive scan, stored blocks) for mt_inflate_write.
+ * mt_inflate_write: the same comp and ws after a scan with status OK, its n_units, n_spans and n_out == total.  The non-empty
+ *   stored blocks of the chained units are listed and copied by the whole grid, then one wave per unit decodes again into its own
+ *   range out[offset, offset + bytes) and nowhere else (the values are checked against the head on the device: a mismatch writes
+ *   nothing).  The output is staged in LDS and leaves in 16-byte stores; matches nearer than 3838 bytes are served from LDS.
+ * mt_inflate_crc: crcs[k] (DEVICE) = CRC-32 of data[k * piece, min(n, (k + 1) * piece)), piece 16 .. 2^24; one entry for n == 0.
+ * Errors: sizes outside these limits, a NULL or misaligned argument are MT_EINVAL, a short ws MT_EWORKSPACE, all before any
+ *   launch; what the stream holds is reported through the status, never through the return value.  Nothing is synchronised. */
+size_t mt_inflate_workspace(long n_comp);
+/* where the workspace keeps what a caller may want to look at after a scan: part 0 = byte offset of the candidate positions
+ * (int32, ascending), 1 = byte offset of the chain (int32 index into the candidates, one per unit), 2 = entries of either table;
+ * 0 for other arguments. */
+size_t mt_inflate_workspace_part(long n_comp, int part);
+int mt_inflate_scan(const uint8_t* comp, long n_comp, long unit_limit, int final, long n_expect, void* ws, size_t ws_bytes,
+                    mt_stream_t stream);
+int mt_inflate_write(const uint8_t* comp, long n_comp, void* ws, size_t ws_bytes, int n_units, int n_spans, uint8_t* out,
+                     long n_out, mt_stream_t stream);
+int mt_inflate_crc(const uint8_t* data, long n, int piece, uint32_t* crcs, mt_stream_t stream);
 /* Connected-component post-processing (remove_all_but_the_largest_connected_component, postprocessing/connected_components.py:48-101).
  * mt_cc_label3d: `lmap, num_objects = scipy.ndimage.label(mask)` (:76) with scipy's default 3-D structure, 6-connectivity (face
  * neighbours only), on the mask {v : member[seg[v]] != 0} of a contiguous uint8 volume seg[D, H, W].  member: HOST array of 256

@@ -153,6 +153,11 @@ SIGNATURES = {
     'mt_deflate_emit': (_i, [_vp, _l, _vp, _i, _i, _vp, _vp, _i, _vp, _sz, _vp, _sz, _vp]),
     'mt_deflate_tokenize_period': (_i, [_vp, _l, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     'mt_deflate_emit_period': (_i, [_vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp, _sz, _vp]),
+    'mt_inflate_workspace': (_sz, [_l]),
+    'mt_inflate_workspace_part': (_sz, [_l, _i]),
+    'mt_inflate_scan': (_i, [_vp, _l, _l, _i, _l, _vp, _sz, _vp]),
+    'mt_inflate_write': (_i, [_vp, _l, _vp, _sz, _i, _i, _vp, _l, _vp]),
+    'mt_inflate_crc': (_i, [_vp, _l, _i, _vp, _vp]),
     'mt_cc_label3d': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'mt_cc_remove': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _i, _d, _vp, _vp]),
     'mt_nonzero_mask': (_i, [_vp, _i, _l, _vp, _vp]),

@@ -12,6 +12,7 @@
 // Tokeniser and framing are restated in tests/deflate_host.py (period 1) and tests/deflate_period_host.py; the device output equals
 // them byte for byte.
 #include "stream_common.h"
+#include "crc32_common.h"
 
 #define DF_THREADS 256
 #define DF_PER 16                                   // bytes per lane and tile: one ds_read_b128
@@ -24,7 +25,6 @@
 #define DF_TOK_EOB 512
 #define DF_TOK_SLOTS 513
 #define DF_HDR_WORDS 256                            // 8192 bits; a dynamic header has at most 14 + 3 + 19*3 + 316*14 = 4498
-#define DF_POLY 0xedb88320u
 #define DF_NOBYTE 256u                              // what stands for a byte in front of the chunk: equal to no byte
 
 // workspace: [prefix 512][token table 513 x 8, padded to 4608][header words 1024][crc u32 x nchunks][size i32 x nchunks][pad 16][regions]
@@ -54,17 +54,6 @@ struct DfStream {
   long npre, n;                              // stream = pre[0, npre) ++ pay[0, n - npre)
   __device__ __forceinline__ uint32_t byte(long i) const { return i < npre ? pre[i] : pay[i - npre]; }
 };
-
-// product of two reflected 32-bit polynomials mod the CRC polynomial (bit 31 is x^0)
-__device__ __forceinline__ uint32_t df_mulmod(uint32_t a, uint32_t b) {
-  uint32_t p = 0;
-#pragma unroll 8
-  for (int k = 0; k < 32; ++k) {
-    p ^= b & (0u - ((a >> (31 - k)) & 1u));
-    b = (b >> 1) ^ (DF_POLY & (0u - (b & 1u)));
-  }
-  return p;
-}
 
 __device__ __forceinline__ int df_length_symbol(int len) {            // RFC 1951 §3.2.5
   if (len == 258) return 285;
@@ -333,19 +322,7 @@ __global__ __launch_bounds__(DF_THREADS) void deflate_tokenize_kernel(DfStream X
   __shared__ DfShared S;
   const int t = threadIdx.x;
   for (int k = t; k < DF_HIST; k += DF_THREADS) S.hist[k] = 0;
-  {
-    uint32_t c = (uint32_t)t;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (DF_POLY & (0u - (c & 1u)));
-    S.crctab[t] = c;
-    uint32_t sq = 1u << 30;                                            // x^1 -> x^128 by 7 squarings
-#pragma unroll 1
-    for (int k = 0; k < 7; ++k) sq = df_mulmod(sq, sq);
-    uint32_t r = 1u << 31;                                             // x^0
-#pragma unroll 1
-    for (int e = t; e; e >>= 1) { if (e & 1) r = df_mulmod(r, sq); sq = df_mulmod(sq, sq); }
-    S.pow128[t] = r;
-  }
+  df_crc_tables(S.crctab, S.pow128, t);
   __syncthreads();
   const long cs = (long)blockIdx.x * chunk;
   const int clen = (int)(X.n - cs < chunk ? X.n - cs : chunk);

@@ -128,21 +128,36 @@ class DatasetAnalyzer(object):
     def _load_case(self, patient_identifier):
         return np.load(os.path.join(self.folder_with_cropped_data, patient_identifier) + ".npz")['data']
 
+    def _load_case_device(self, patient_identifier, device=None):
+        """the cropped case [C + 1, X, Y, Z] as a device tensor: its compressed bytes are uploaded and inflated there
+        (utilities.npz_io.load_npz_device); a file of another writer is read by `np.load` inside the reader.
+        device None: the calling thread's current device."""
+        from ..utilities.npz_io import load_npz_device
+        fname = os.path.join(self.folder_with_cropped_data, patient_identifier) + ".npz"
+        return load_npz_device(fname, 'data', torch.device('cuda', torch.cuda.current_device()) if device is None else device)
+
+    @staticmethod
+    def _float32_on_device(a, dev='cuda'):
+        if torch.is_tensor(a):
+            return a.to(device=dev, dtype=torch.float32).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+
     def _prefetched_cases(self):
-        """(identifier, array) in order; up to num_processes files are read and decompressed ahead on host threads."""
+        """(identifier, array) in order; up to num_processes files are read (and inflated, on the device) ahead from host threads."""
         ahead = max(1, int(self.num_processes))
+        dev = torch.device('cuda', torch.cuda.current_device())          # the caller's device (the current one is per thread)
         with ThreadPoolExecutor(max_workers=ahead) as pool:
             pending = []
             ids = iter(self.patient_identifiers)
             for p in ids:
-                pending.append((p, pool.submit(self._load_case, p)))
+                pending.append((p, pool.submit(self._load_case_device, p, dev)))
                 if len(pending) >= ahead:
                     break
             while pending:
                 p, fut = pending.pop(0)
                 nxt = next(ids, None)
                 if nxt is not None:
-                    pending.append((nxt, pool.submit(self._load_case, nxt)))
+                    pending.append((nxt, pool.submit(self._load_case_device, nxt, dev)))
                 yield p, fut.result()
 
     def analyse_segmentations(self):
@@ -152,9 +167,10 @@ class DatasetAnalyzer(object):
                 _no_device()
             props_per_patient = OrderedDict()
             for p, all_data in self._prefetched_cases():
-                seg = torch.from_numpy(np.ascontiguousarray(all_data[-1], dtype=np.float32)).cuda()
+                seg = self._float32_on_device(all_data[-1])
                 labels = ops.label_presence(seg, "the segmentation of case %s" % p)
-                props_per_patient[p] = {'has_classes': np.array(labels, dtype=all_data.dtype)}       # np.unique(seg)
+                dtype = np.dtype(str(all_data.dtype).replace('torch.', ''))
+                props_per_patient[p] = {'has_classes': np.array(labels, dtype=dtype)}       # np.unique(seg)
             with open(self.props_per_case_file, 'wb') as f:
                 pickle.dump(props_per_patient, f)
         else:
@@ -218,7 +234,7 @@ class DatasetAnalyzer(object):
                 continue
             if all_data.shape[0] < M + 1:
                 raise ValueError("case %s holds %d modalities, %d expected" % (p, all_data.shape[0] - 1, M))
-            vol = torch.from_numpy(np.ascontiguousarray(all_data, dtype=np.float32)).to(dev)
+            vol = self._float32_on_device(all_data, dev)
             vol = vol.reshape(vol.shape[0], -1)
             data, seg = vol[:M], vol[-1]
             index = ops.fg_sample_count(seg)

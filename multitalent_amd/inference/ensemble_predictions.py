@@ -6,8 +6,8 @@ under `not_postprocessed/`, the post-processed ones in `<out>` and a copy of the
 What is different underneath: the reference's `np.vstack` -> `np.mean` -> argmax / region thresholds -> insertion into the uncropped
 volume (four host passes over K*C*V elements) is ONE kernel, `mt_ensemble_classify`, which reproduces numpy's float16 mean bit for
 bit and decides the label on it.  The members are the stored probabilities at the original grid, so nothing is resampled: a member
-whose shape is not `size_after_cropping` (neither exporter writes one) is refused.  `threads` is accepted and ignored; the members of
-the next case are decompressed on one host thread while the current case is on the device."""
+whose shape is not `size_after_cropping` (neither exporter writes one) is refused.  `threads` is accepted and ignored; the compressed
+members of the next case are read and inflated on the device from one host thread while the current case is merged."""
 import argparse
 import os
 import pickle
@@ -55,12 +55,16 @@ def ensemble_classify(members, C, shape, chan_stride, out, offset, class_order=N
 
 
 def upload_member(arr, device):
-    """float16 [C, X, Y, Z] on the host -> [C, padded_stride(V)] on the device (the pad is never read as a voxel)."""
+    """float16 [C, X, Y, Z], on the host or (read by `load_npz_device`) on the device -> [C, padded_stride(V)] on the device (the
+    pad is never read as a voxel)."""
     import torch
     C = int(arr.shape[0])
     V = int(np.prod(arr.shape[1:]))
     buf = torch.empty((C, padded_stride(V)), dtype=torch.float16, device=device)
-    buf[:, :V].copy_(torch.from_numpy(np.ascontiguousarray(arr).reshape(C, V)))
+    if torch.is_tensor(arr):
+        buf[:, :V].copy_(arr.reshape(C, V))
+    else:
+        buf[:, :V].copy_(torch.from_numpy(np.ascontiguousarray(arr).reshape(C, V)))
     return buf
 
 
@@ -105,16 +109,27 @@ def _load_pickle(f):
         return pickle.load(fh)
 
 
-def _load_case(files, properties_files):
-    """Host side of one case: the K members and their properties, with every rejection that needs no device."""
+def _read_member(f, device=None):
+    """the stored probabilities of one member: inflated on `device` (utilities.npz_io.load_npz_device; a file of another writer
+    falls back to np.load there) when there is one, so that the rejections below still work without.  device None: the calling
+    thread's current device — a pool thread passes the one its caller selected."""
+    import torch
+    if torch.cuda.is_available():
+        from ..utilities.npz_io import load_npz_device
+        return load_npz_device(f, 'softmax', torch.device('cuda', torch.cuda.current_device()) if device is None else device)
+    return np.load(f)['softmax']
+
+
+def _load_case(files, properties_files, device=None):
+    """One case: the K members (device tensors when there is a device) and their properties, with every rejection."""
     if len(files) > MAX_MEMBERS:
         raise ValueError("an ensemble takes at most %d members, got %d: %s" % (MAX_MEMBERS, len(files), str(files)))
     props = [_load_pickle(f) for f in properties_files]
     after = tuple(int(i) for i in props[0]['size_after_cropping'])
     arrays = []
     for f in files:
-        a = np.load(f)['softmax']
-        if a.dtype != np.float16:
+        a = _read_member(f, device)
+        if str(a.dtype).replace('torch.', '') != 'float16':
             raise TypeError("%s: softmax is %s, the exporters store float16" % (f, a.dtype))
         if tuple(a.shape[1:]) != after or (arrays and a.shape != arrays[0].shape):
             raise NotImplementedError("%s: softmax of shape %s, size_after_cropping is %s: stored probabilities are at the original "
@@ -173,11 +188,13 @@ def merge(folders, output_folder, threads, override=True, postprocessing_file=No
         if override or not os.path.isfile(out_file):
             jobs.append(([os.path.join(f, p + ".npz") for f in folders], [os.path.join(f, p + ".pkl") for f in folders], out_file))
     # the members of the next case are read and decompressed while the current one is on the device
+    import torch
+    device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else None     # (per thread: handed to the pool)
     with ThreadPoolExecutor(1) as ex:
-        nxt = ex.submit(_load_case, jobs[0][0], jobs[0][1]) if jobs else None
+        nxt = ex.submit(_load_case, jobs[0][0], jobs[0][1], device) if jobs else None
         for n, (files, property_files, out_file) in enumerate(jobs):
             loaded = nxt.result()
-            nxt = ex.submit(_load_case, jobs[n + 1][0], jobs[n + 1][1]) if n + 1 < len(jobs) else None
+            nxt = ex.submit(_load_case, jobs[n + 1][0], jobs[n + 1][1], device) if n + 1 < len(jobs) else None
             merge_files(files, property_files, out_file, True, store_npz, _loaded=loaded)
 
     if postprocessing_file is not None:

@@ -1487,5 +1487,81 @@ class deflate_segments(object):
                 return
 
 
+_READ = "the INFLATE decoder of the file readers runs"
+INFLATE_UNIT_LIMIT = 16 * DEFLATE_CHUNK
+INFLATE_CRC_PIECE = 1 << 20
+INFLATE_STATUS = ('OK', 'FOREIGN', 'TOO_LONG', 'BAD', 'CORRUPT', 'SIZE')
+
+
+class InflateForeign(Exception):
+    """the stream is well-formed as far as it was looked at, but has no restart points the decoder can work from (too many
+    candidates, or a unit that is longer than `unit_limit`): a file of another writer, which the host inflates"""
+
+
+def _inflate_unit_starts(ws, n, units):
+    """the chained units' start positions as a device int32 tensor, from the workspace of mt_inflate_scan"""
+    lib = _lib.load()
+    cand, ucand, cap = (int(lib.mt_inflate_workspace_part(n, k)) for k in range(3))
+    return ws[cand:cand + 4 * cap].view(torch.int32)[ws[ucand:ucand + 4 * units].view(torch.int32).long()]
+
+
+def inflate_raw(comp, n_out=None, unit_limit=INFLATE_UNIT_LIMIT, final=True, stages=None, want_starts=False):
+    """comp: uint8 device tensor (1-D, contiguous, any alignment) holding one raw DEFLATE stream -> (uint8 device tensor of the
+    decoded bytes, their CRC-32, info).  n_out: the size the caller expects (a different size is an IOError).  final=False
+    accepts a stream that ends on a restart marker with no last block (ops.deflate_raw(..., final=False)).  The stream is decoded
+    in parallel from its restart points (mt_inflate_scan / mt_inflate_write); one without them (more than `unit_limit` bytes in
+    one unit) raises InflateForeign, a malformed one IOError.  info: {'status', 'units', 'candidates', 'spans', 'bytes'} and, with
+    want_starts, 'starts': the units' start positions as a device tensor; stages receives the seconds spent in 'scan', 'write' and 'crc'."""
+    import time
+    from .utilities import deflate_host as H
+    _require_device(_READ, comp)
+    if comp.dtype != torch.uint8 or comp.dim() != 1 or not comp.is_contiguous():
+        raise ValueError("inflate_raw: a contiguous 1-D uint8 device tensor is expected, got %s %s" % (comp.dtype, tuple(comp.shape)))
+    n = int(comp.numel())
+    lib = _lib.load()
+    t0 = time.perf_counter()
+    with torch.cuda.device(comp.device):
+        ws_bytes = int(lib.mt_inflate_workspace(n))
+        if not ws_bytes:
+            raise ValueError("inflate_raw: %d compressed bytes; 1 .. 2^31 - 65 are decoded as one stream" % n)
+        ws = _deflate_alloc(ws_bytes, comp.device)
+        _lib.check(lib.mt_inflate_scan(_ptr(comp), n, int(unit_limit), 1 if final else 0, -1 if n_out is None else int(n_out),
+                                       _ptr(ws), ws_bytes, _stream()), 'inflate_scan')
+        head = ws[:24].cpu().numpy()
+        status, units = int(head[:4].view(np.int32)[0]), int(head[4:8].view(np.int32)[0])
+        total = int(head[8:16].view(np.int64)[0])
+        cands, spans = int(head[16:20].view(np.int32)[0]), int(head[20:24].view(np.int32)[0])
+        info = {'status': INFLATE_STATUS[status] if 0 <= status < len(INFLATE_STATUS) else status, 'units': units, 'candidates': cands,
+                'spans': spans, 'bytes': total}
+        t1 = time.perf_counter()
+        if stages is not None:
+            stages['scan'] = stages.get('scan', 0.0) + (t1 - t0)
+        err = None
+        if info['status'] in ('FOREIGN', 'TOO_LONG'):
+            err = InflateForeign("inflate_raw: %s: %d candidates in %d bytes, unit limit %d" % (info['status'], cands, n, unit_limit))
+        elif info['status'] == 'SIZE':
+            err = IOError("inflate_raw: the stream holds %d bytes, %d were expected" % (total, n_out))
+        elif info['status'] != 'OK':
+            err = IOError("inflate_raw: the DEFLATE stream is damaged (%s)" % info['status'])
+        if err is not None:
+            err.info = info
+            raise err
+        if want_starts:
+            info['starts'] = _inflate_unit_starts(ws, n, units)
+        out = _deflate_alloc(total, comp.device)
+        _lib.check(lib.mt_inflate_write(_ptr(comp), n, _ptr(ws), ws_bytes, units, spans, _ptr(out), total, _stream()), 'inflate_write')
+        if stages is not None:
+            torch.cuda.synchronize(comp.device)
+            t2 = time.perf_counter()
+            stages['write'] = stages.get('write', 0.0) + (t2 - t1)
+        pieces = max(1, -(-total // INFLATE_CRC_PIECE))
+        crcs = torch.empty(pieces, dtype=torch.int32, device=comp.device)
+        _lib.check(lib.mt_inflate_crc(_ptr(out), total, INFLATE_CRC_PIECE, _ptr(crcs), _stream()), 'inflate_crc')
+        crc = H.crc32_join(crcs.cpu().numpy().view(np.uint32), INFLATE_CRC_PIECE, total - (pieces - 1) * INFLATE_CRC_PIECE)
+        if stages is not None:
+            stages['crc'] = stages.get('crc', 0.0) + (time.perf_counter() - t2)
+    return out, crc, info
+
+
 _parse_select_env()
 _select_env = _select

@@ -17,7 +17,7 @@ import torch
 
 from .. import ops
 from ..evaluation.evaluator import aggregate_scores
-from ..utilities.nifti_io import read_image, write_image
+from ..utilities.nifti_io import Image, read_image, read_image_device, write_image
 
 default_num_threads = 8
 
@@ -103,10 +103,19 @@ def remove_all_but_the_largest_connected_component(image, for_which_classes, vol
 
 def load_remove_save(input_file, output_file, for_which_classes, minimum_valid_object_size=None):
     """connected_components.py:30-45: the file's geometry is kept, volume_per_voxel = prod(spacing) in fp64."""
-    img = read_image(input_file)
-    img_npy = np.asarray(img.array)
+    if input_file.endswith('.nii.gz') and output_file.endswith('.nii.gz') and torch.cuda.is_available():
+        # inflated on the device (utilities.nifti_io.read_image_device, DESIGN §6y); a uint8 label map never visits the host
+        vox, spacing, origin, direction = read_image_device(input_file, torch.device('cuda', torch.cuda.current_device()))
+        img = Image(vox if vox.dtype == torch.uint8 else vox.cpu().numpy(), spacing, origin, direction)
+    else:
+        img = read_image(input_file)
     volume_per_voxel = float(np.prod(img.spacing, dtype=np.float64))
-    if img_npy.dtype == np.uint8 and img_npy.ndim == 3 and output_file.endswith('.nii.gz'):
+    if torch.is_tensor(img.array):
+        ops.cc_check_shape(tuple(img.array.shape))
+        img_npy = img.array
+    else:
+        img_npy = np.asarray(img.array)
+    if not torch.is_tensor(img_npy) and img_npy.dtype == np.uint8 and img_npy.ndim == 3 and output_file.endswith('.nii.gz'):
         # the label map stays on the device after the removal and is written from there (utilities.nifti_io.write_label_map_device)
         ops.cc_check_shape(img_npy.shape)
         img_npy = _to_device_uint8(img_npy)[0]

@@ -33,8 +33,14 @@ class GenericPreprocessor(object):
 
     @staticmethod
     def load_cropped(cropped_output_dir, case_identifier):
-        all_data = np.load(os.path.join(cropped_output_dir, "%s.npz" % case_identifier))['data']
-        data = all_data[:-1].astype(np.float32)
+        fname = os.path.join(cropped_output_dir, "%s.npz" % case_identifier)
+        if torch.cuda.is_available():        # inflated on the device (utilities.npz_io.load_npz_device): device tensors
+            from ..utilities.npz_io import load_npz_device
+            all_data = load_npz_device(fname, 'data', torch.device('cuda', torch.cuda.current_device()))
+            data = all_data[:-1].float()
+        else:
+            all_data = np.load(fname)['data']
+            data = all_data[:-1].astype(np.float32)
         seg = all_data[-1:]
         with open(os.path.join(cropped_output_dir, "%s.pkl" % case_identifier), 'rb') as f:
             properties = pickle.load(f)

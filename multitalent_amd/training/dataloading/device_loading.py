@@ -24,11 +24,15 @@ from .dataset_loading import DataLoader3D, load_pickle
 ResidentCase = namedtuple('ResidentCase', 'data seg shape properties')      # data [C, x, y, z] f32, seg [x, y, z] int16: device
 
 
-def _case_file_array(entry):
-    """The whole [C+1, x, y, z] array of a case: the unpacked .npy when present, else the .npz (DataLoader3D._load_case)."""
+def _case_file_array(entry, device=None):
+    """The whole [C+1, x, y, z] array of a case: the unpacked .npy when present, else the .npz (DataLoader3D._load_case) — with a
+    `device`, inflated there (utilities.npz_io.load_npz_device) and returned as a device tensor."""
     f = entry['data_file']
     if os.path.isfile(f[:-4] + ".npy"):
         return np.load(f[:-4] + ".npy", 'r')
+    if device is not None:
+        from ...utilities.npz_io import load_npz_device
+        return load_npz_device(f, 'data', device)
     return np.load(f)['data']
 
 
@@ -66,6 +70,19 @@ class DeviceCaseCache:
     def get(self, data_file):
         return self._cases.get(data_file)
 
+    def room_for(self, entry):
+        """False when the case of `entry` is known not to fit what is left of the budget.  For a case that exists as .npz only the
+        shape comes from the .npy header at the head of the member (utilities.npz_io.peek_npy_header: nothing else is inflated);
+        where it cannot be told this way the answer is True and `admit` decides on the array."""
+        if self.used_bytes >= self.budget_bytes:
+            return False
+        f = entry['data_file']
+        if os.path.isfile(f[:-4] + ".npy") or not os.path.isfile(f):
+            return True
+        from ...utilities.npz_io import peek_npy_header
+        head = peek_npy_header(f, 'data')
+        return head is None or len(head[0]) != 4 or self.used_bytes + self.case_bytes(head[0]) <= self.budget_bytes
+
     def admit(self, entry, all_data=None, properties=None):
         """entry: a `load_dataset` entry.  -> its ResidentCase (uploading it now when it fits the budget), or None.
         all_data / properties: what the caller has already read of the case."""
@@ -74,7 +91,9 @@ class DeviceCaseCache:
         if res is not None:
             return res
         if all_data is None:
-            all_data = _case_file_array(entry)
+            if not self.room_for(entry):
+                return None                  # known from the header alone: nothing is read or inflated for a case that cannot stay
+            all_data = _case_file_array(entry, self.device)
         need = self.case_bytes(all_data.shape)
         if self.used_bytes + need > self.budget_bytes:
             return None
@@ -83,15 +102,23 @@ class DeviceCaseCache:
         from ... import ops
         c, shape = all_data.shape[0] - 1, tuple(int(i) for i in all_data.shape[1:])
         v = int(np.prod(shape, dtype=np.int64))
-        if self._pinned is None or self._pinned.numel() < (c + 1) * v:
-            self._pinned = None
-            self._pinned = torch.empty((c + 1) * v, dtype=torch.float32).pin_memory()
-        np.copyto(self._pinned.numpy()[:(c + 1) * v].reshape(all_data.shape), all_data)
+        on_device = torch.is_tensor(all_data) and all_data.is_cuda and all_data.dtype == torch.float32
+        if torch.is_tensor(all_data) and not on_device:
+            all_data = all_data.float().cpu().numpy()
+        if not on_device:
+            if self._pinned is None or self._pinned.numel() < (c + 1) * v:
+                self._pinned = None
+                self._pinned = torch.empty((c + 1) * v, dtype=torch.float32).pin_memory()
+            np.copyto(self._pinned.numpy()[:(c + 1) * v].reshape(all_data.shape), all_data)
         with torch.cuda.device(self.device):
-            data = torch.empty((c,) + shape, dtype=torch.float32, device=self.device)
-            data.view(-1).copy_(self._pinned[:c * v], non_blocking=True)
-            segf = torch.empty(shape, dtype=torch.float32, device=self.device)
-            segf.view(-1).copy_(self._pinned[c * v:(c + 1) * v], non_blocking=True)
+            if on_device:                    # read by load_npz_device: the channels are copied out of the inflated member,
+                data, segf = all_data[:c].clone(), all_data[c].clone()      # which is then free again
+                del all_data
+            else:
+                data = torch.empty((c,) + shape, dtype=torch.float32, device=self.device)
+                data.view(-1).copy_(self._pinned[:c * v], non_blocking=True)
+                segf = torch.empty(shape, dtype=torch.float32, device=self.device)
+                segf.view(-1).copy_(self._pinned[c * v:(c + 1) * v], non_blocking=True)
             flag = torch.zeros(1, dtype=torch.int32, device=self.device)
             seg = ops.seg_narrow(segf, flag)
             bad = int(flag.item())           # the one synchronisation of an upload: the staging buffer is free again after it
@@ -139,11 +166,24 @@ class DeviceDataLoader3D(DataLoader3D):
         self._slots = [_Slot() for _ in range(self.batch_size)]
         self._flags = None
 
+    def determine_shapes(self):
+        """as DataLoader3D's; the channel count of a first case that exists as .npz only comes from the .npy header at the head of
+        the member, so that no case is inflated on the host just to be counted"""
+        entry = self._data[list(self._data.keys())[0]]
+        f = entry['data_file']
+        if not os.path.isfile(f[:-4] + ".npy") and os.path.isfile(f):
+            from ...utilities.npz_io import peek_npy_header
+            head = peek_npy_header(f, 'data')
+            if head is not None and len(head[0]) == 4:
+                return (self.batch_size, head[0][0] - 1, *self.patch_size), (self.batch_size, 1, *self.patch_size)
+        return super().determine_shapes()
+
     def plan_batch(self):
-        """The host half of generate_train_batch, without a device: exactly its draws from numpy's global stream, in its order (the
+        """The host half of generate_train_batch (without a cache, without a device): exactly its draws from numpy's global stream, in its order (the
         keys; per sample the foreground class and voxel, or three randint).  -> {'keys', 'properties' [B], 'bb_lb' [B][3] (lower
         corner of each patch in case coordinates, may be negative), 'shapes' [B][3], 'entries' [B], 'cases' [B] (the opened array of
-        a sample whose case is not resident, else None)}."""
+        a sample whose case is not resident, else None)}.  With a cache, a case that exists as .npz only and fits the budget is
+        admitted here, through the device reader; the host opens (and inflates) only a case that will be staged."""
         selected_keys = np.random.choice(self.list_of_keys, self.batch_size, True, self.sampling_probabilities)
         plan = {'keys': selected_keys, 'properties': [], 'bb_lb': [], 'shapes': [], 'entries': [], 'cases': []}
         for j, i in enumerate(selected_keys):
@@ -154,8 +194,15 @@ class DeviceDataLoader3D(DataLoader3D):
                 properties, case_all_data, shape = res.properties, None, res.shape
             else:
                 properties = entry['properties'] if 'properties' in entry.keys() else load_pickle(entry['properties_file'])
-                case_all_data = self._load_case(entry)
-                shape = tuple(int(s) for s in case_all_data.shape[1:])
+                if self.cache is not None and not os.path.isfile(entry['data_file'][:-4] + ".npy") and self.cache.room_for(entry):
+                    # a case that exists as .npz only and still fits: it goes resident now, inflated on the device
+                    # (DeviceCaseCache.admit -> utilities.npz_io.load_npz_device), and never exists uncompressed on the host
+                    res = self.cache.admit(entry, None, properties)
+                if res is not None:
+                    case_all_data, shape = None, res.shape
+                else:
+                    case_all_data = self._load_case(entry)
+                    shape = tuple(int(s) for s in case_all_data.shape[1:])
             need_to_pad = self.need_to_pad.copy()
             for d in range(3):
                 if need_to_pad[d] + shape[d] < self.patch_size[d]:

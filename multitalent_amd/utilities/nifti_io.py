@@ -6,7 +6,8 @@ codec below (single-file format, little endian, scalar volumes, sform or qform g
 maps, nothing else.  Geometry follows ITK's conventions so that the `itk_*` properties of a case mean the same thing either
 way: arrays are indexed [z, y, x], spacing / origin are (x, y, z), the direction is the row-major 3x3 cosine matrix in LPS
 (NIfTI stores RAS: x and y are negated on the way in and out).  Host code, with one exception: a uint8 label map that is already
-on the device and goes to a `.nii.gz` is gzip-encoded there (`write_label_map_device`), behind the same header."""
+on the device and goes to a `.nii.gz` is gzip-encoded there (`write_label_map_device`), behind the same header, and
+`read_image_device` inflates a `.nii.gz` on the device."""
 import gzip
 import struct
 
@@ -89,10 +90,9 @@ def _matrix_to_quaternion(R):
     return float(b), float(c), float(d), qfac
 
 
-def _read_nifti(fname):
-    opener = gzip.open if fname.endswith('.gz') else open
-    with opener(fname, 'rb') as f:
-        raw = f.read()
+def _parse_nifti(raw, fname):
+    """raw: at least the 348 header bytes of a single-file NIfTI-1 -> (dtype with the file's byte order, (nz, ny, nx), voxel offset,
+    slope, intercept, spacing, origin, direction), geometry in ITK's conventions"""
     if len(raw) < 348:
         raise IOError("%s: not a NIfTI-1 file (shorter than its header)" % fname)
     end = '<'
@@ -114,11 +114,6 @@ def _read_nifti(fname):
         raise IOError("%s: only 3D scalar volumes are supported (dim = %s)" % (fname, str(dim)))
     nx, ny, nz = dim[1:4]
     dt = np.dtype(_DTYPES[datatype]).newbyteorder(end)
-    off = int(vox_offset)
-    arr = np.frombuffer(raw, dtype=dt, count=nx * ny * nz, offset=off).reshape(nz, ny, nx)
-    arr = arr.astype(dt.newbyteorder('='))
-    if slope != 0 and not (slope == 1 and inter == 0) and np.isfinite(slope):
-        arr = arr.astype(np.float64) * slope + inter
     # geometry precedence as ITK's NiftiImageIO (the reference reads through SimpleITK): the qform (rotation from the quaternion, spacing
     # from pixdim) when qform_code > 0, else the sform (spacing = column norms); a file whose two transforms disagree then gives the
     # same spacing / direction whether or not SimpleITK is installed
@@ -133,7 +128,93 @@ def _read_nifti(fname):
         Rras = M / spacing
     else:
         Rras, spacing, t = np.diag([-1.0, -1.0, 1.0]), np.abs(np.array(pixdim[1:4], dtype=np.float64)), np.zeros(3)
-    return Image(arr, spacing, _LPS @ t, (_LPS @ Rras).ravel())
+    return dt, (nz, ny, nx), int(vox_offset), slope, inter, spacing, _LPS @ t, (_LPS @ Rras).ravel()
+
+
+def _is_scaled(slope, inter):
+    return bool(slope != 0 and not (slope == 1 and inter == 0) and np.isfinite(slope))
+
+
+def _read_nifti(fname):
+    opener = gzip.open if fname.endswith('.gz') else open
+    with opener(fname, 'rb') as f:
+        raw = f.read()
+    dt, (nz, ny, nx), off, slope, inter, spacing, origin, direction = _parse_nifti(raw, fname)
+    arr = np.frombuffer(raw, dtype=dt, count=nx * ny * nz, offset=off).reshape(nz, ny, nx)
+    arr = arr.astype(dt.newbyteorder('='))
+    if _is_scaled(slope, inter):
+        arr = arr.astype(np.float64) * slope + inter
+    return Image(arr, spacing, origin, direction)
+
+
+def gzip_payload(blob, fname=''):
+    """blob: one gzip member -> (offset and length of its raw DEFLATE stream, CRC-32, ISIZE).  FEXTRA, FNAME, FCOMMENT and FHCRC
+    are honoured (RFC 1952)."""
+    if len(blob) < 18 or blob[:2] != b'\x1f\x8b' or blob[2] != 8:
+        raise IOError("%s: not a gzip member with a DEFLATE stream" % fname)
+    flags, p = blob[3], 10
+    try:
+        if flags & 4:
+            p += 2 + struct.unpack('<H', blob[p:p + 2])[0]
+        for bit in (8, 16):
+            if flags & bit:
+                p = blob.index(b'\0', p) + 1
+    except (ValueError, struct.error):
+        raise IOError("%s: the gzip header is cut short" % fname)
+    if flags & 2:
+        p += 2
+    if p + 8 >= len(blob):
+        raise IOError("%s: the gzip header is cut short" % fname)
+    crc, isize = struct.unpack('<II', blob[-8:])
+    return p, len(blob) - 8 - p, crc, isize
+
+
+def read_image_device(fname, device, stages=None):
+    """A `.nii.gz` volume read onto the device: the file's compressed bytes are uploaded and inflated there (ops.inflate_raw,
+    DESIGN §6y), CRC-32 and ISIZE of the gzip trailer are checked, the header comes back and is parsed by `_parse_nifti`, and the
+    voxels are a view behind it -> (device tensor [z, y, x], spacing, origin, direction).  A stream without restart points or one
+    the unit rules refuse (a file of another writer; a damaged one is then refused by zlib), a non-native byte order or a slope /
+    intercept takes the host path: `read_image` and an upload.  A trailer that differs after a successful decode is an IOError.
+    stages['path'] says 'device' or 'host'; the seconds of 'file', 'upload', 'scan', 'write' and 'crc' are added."""
+    import time
+    import torch
+    from .. import ops
+    fname = str(fname)
+    t0 = time.perf_counter()
+    with open(fname, 'rb') as f:
+        blob = f.read()
+    p, n, crc, isize = gzip_payload(blob, fname)
+    t1 = time.perf_counter()
+    comp = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8, count=n, offset=p).copy()).to(device)
+    if stages is not None:
+        torch.cuda.synchronize(comp.device)
+        stages['file'] = stages.get('file', 0.0) + (t1 - t0)
+        stages['upload'] = stages.get('upload', 0.0) + (time.perf_counter() - t1)
+    try:
+        out, got, _ = ops.inflate_raw(comp, stages=stages)
+    except (ops.InflateForeign, IOError):
+        # no restart points, or a stream the unit rules refuse (BAD / CORRUPT: a valid sync-flushed stream of zlib or pigz is one):
+        # the host reader decides, and zlib refuses a file that is really damaged
+        out = None
+    if out is not None:
+        if got != crc or (int(out.numel()) & 0xffffffff) != isize:
+            raise IOError("%s: CRC-32 / size of the decoded bytes (%08x, %d) differ from the gzip trailer (%08x, %d)"
+                          % (fname, got, int(out.numel()), crc, isize))
+        raw = out[:352].cpu().numpy().tobytes()
+        dt, shape, off, slope, inter, spacing, origin, direction = _parse_nifti(raw, fname)
+        count = shape[0] * shape[1] * shape[2]
+        if dt.isnative and not _is_scaled(slope, inter) and off % dt.itemsize == 0 and hasattr(torch, dt.name):
+            if off + count * dt.itemsize > int(out.numel()):
+                raise IOError("%s: the file ends inside its voxels" % fname)
+            if stages is not None:
+                stages['path'] = 'device'
+            vox = out[off:off + count * dt.itemsize].view(getattr(torch, dt.name)).reshape(shape)
+            return vox, tuple(float(i) for i in spacing), tuple(float(i) for i in origin), tuple(float(i) for i in direction)
+    if stages is not None:
+        stages['path'] = 'host'
+    im = read_image(fname)
+    arr = np.ascontiguousarray(im.array)
+    return torch.from_numpy(arr).to(device), im.spacing, im.origin, im.direction
 
 
 def _nifti_header(shape, dtype, spacing, origin, direction):

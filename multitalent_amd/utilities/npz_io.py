@@ -8,7 +8,8 @@ host prefix, the bytes stay on the device and are DEFLATE-encoded there with run
 (ops.deflate_segments: segments of at most 1 GiB, concatenated into one raw stream), and only compressed bytes reach the host.
 The zip structures — local header, central directory, end record, with Zip64 fields where a size or offset does not fit 32 bits — are
 written here by hand: CRC-32 and sizes stand in the local header (patched once the member is written, no data descriptor), the
-file is written under a temporary name and renamed.  `np.load` reads the result; reading and inflating are not part of this."""
+file is written under a temporary name and renamed.  `np.load` reads the result; `load_npz_device` below reads a member back onto the
+device, where it is inflated in parallel from the restart points the encoder leaves behind its chunks."""
 import io
 import os
 import struct
@@ -145,3 +146,145 @@ def encode_npz_device(_stages=None, **device_tensors):
         bodies = list(seg)
         out.append((key, n, HostBodies(bodies, seg.crc)))
     return out
+
+
+# ---- reading: the member's compressed bytes go to the device and are inflated there (ops.inflate_raw) ----
+_MAX_COMPRESSED = 2 ** 31 - 65           # what one mt_inflate_scan takes
+
+
+def locate_member(fname, key):
+    """-> dict(method, flags, offset, csize, usize, crc) of the member `<key>.npy`: sizes and CRC-32 from the central directory
+    (`zipfile` reads it, Zip64 included), the data offset from the local header in front of the member."""
+    import zipfile
+    with zipfile.ZipFile(fname) as z:
+        try:
+            info = z.getinfo(str(key) + '.npy')
+        except KeyError:
+            raise KeyError("%s is not a file in the archive %s" % (key, fname))
+    with open(fname, 'rb') as f:
+        f.seek(info.header_offset)
+        local = f.read(30)
+    if len(local) != 30 or local[:4] != b'PK\x03\x04':
+        raise IOError("%s: no local file header in front of member %s" % (fname, key))
+    nlen, elen = struct.unpack('<HH', local[26:30])
+    return {'method': info.compress_type, 'flags': info.flag_bits, 'offset': info.header_offset + 30 + nlen + elen,
+            'csize': info.compress_size, 'usize': info.file_size, 'crc': info.CRC}
+
+
+def parse_npy_header(first):
+    """first: the leading bytes of a .npy stream -> (shape, fortran_order, dtype, header bytes), or None when they do not hold the
+    whole header (its length then stands in bytes 8..11)"""
+    f = io.BytesIO(bytes(first))
+    try:
+        version = np.lib.format.read_magic(f)
+        if version == (1, 0):
+            shape, fortran, dtype = np.lib.format.read_array_header_1_0(f)
+        elif version == (2, 0):
+            shape, fortran, dtype = np.lib.format.read_array_header_2_0(f)
+        else:
+            raise IOError("a .npy stream of version %s" % (version,))
+    except ValueError as e:
+        if len(first) < 12 or len(first) < npy_header_bytes(first):
+            return None
+        raise IOError("not a .npy stream: %s" % e)
+    return tuple(int(s) for s in shape), bool(fortran), dtype, f.tell()
+
+
+def npy_header_bytes(first):
+    """the size of the .npy header whose first 12 bytes are given"""
+    major = first[6]
+    return 10 + struct.unpack('<H', first[8:10])[0] if major == 1 else 12 + struct.unpack('<I', first[8:12])[0]
+
+
+def _load_host(fname, key, device, stages):
+    import torch
+    if stages is not None:
+        stages['path'] = 'host'
+    with np.load(fname) as z:
+        arr = z[key]
+    return torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+
+
+def load_npz_device(fname, key, device, fallback=True, stages=None):
+    """`np.load(fname)[key]` as a tensor on `device`, for a file this package's writers made: only the member's compressed bytes are
+    read and uploaded, they are inflated on the device, size and CRC-32 are checked against the zip header (a mismatch is an
+    IOError), the .npy header comes back and is parsed by numpy's own `np.lib.format`, and the result is a view behind the header.
+    A stored member, Fortran order, an object dtype or one outside the writer's list, a stream without restart points (a file
+    of another writer: ops.InflateForeign) and a stream the unit rules refuse (BAD / CORRUPT / another size: a sync-flushed stream of
+    another writer is one; a damaged file is then refused by zlib) are read by `np.load` and uploaded when `fallback` is set, and
+    raise otherwise.  A CRC-32 mismatch after a successful decode is always an IOError.
+    stages['path'] says 'device' or 'host'; the seconds of 'file', 'upload', 'scan', 'write', 'crc' and 'header' are added."""
+    import time
+    import torch
+    from .. import ops
+    fname = str(fname)
+    t0 = time.perf_counter()
+    m = locate_member(fname, key)
+
+    def host(why):
+        if not fallback:
+            raise ValueError("load_npz_device: %s[%s] is not read on the device: %s" % (fname, key, why))
+        return _load_host(fname, key, device, stages)
+
+    if m['method'] != 8 or m['flags'] & 0x9 or not 0 < m['csize'] <= _MAX_COMPRESSED:
+        return host("method %d, flags %#x, %d compressed bytes" % (m['method'], m['flags'], m['csize']))
+    with open(fname, 'rb') as f:
+        f.seek(m['offset'])
+        buf = np.fromfile(f, dtype=np.uint8, count=m['csize'])
+    if buf.size != m['csize']:
+        raise IOError("%s: member %s is cut short" % (fname, key))
+    t1 = time.perf_counter()
+    comp = torch.from_numpy(buf).to(device)
+    if stages is not None:
+        torch.cuda.synchronize(comp.device)
+        stages['file'] = stages.get('file', 0.0) + (t1 - t0)
+        stages['upload'] = stages.get('upload', 0.0) + (time.perf_counter() - t1)
+    try:
+        out, crc, _ = ops.inflate_raw(comp, n_out=m['usize'], stages=stages)
+    except ops.InflateForeign as e:
+        return host(str(e))
+    except IOError as e:
+        # BAD / CORRUPT / a size mismatch are verdicts of the UNIT rules: a valid stream of another writer that holds empty stored
+        # blocks without a dictionary reset behind them (zlib's Z_SYNC_FLUSH, pigz) fails them too, so zlib decides what is damaged
+        if not fallback:
+            raise
+        return host(str(e))
+    t2 = time.perf_counter()
+    if crc != m['crc']:
+        raise IOError("%s: CRC-32 of member %s is %08x, its header says %08x" % (fname, key, crc, m['crc']))
+    first = out[:min(m['usize'], 4096)].cpu().numpy().tobytes()
+    head = parse_npy_header(first)
+    if head is None and len(first) >= 12:
+        head = parse_npy_header(out[:min(m['usize'], npy_header_bytes(first))].cpu().numpy().tobytes())
+    if head is None:
+        raise IOError("%s: member %s is no .npy stream" % (fname, key))
+    shape, fortran, dtype, hbytes = head
+    count = int(np.prod(shape, dtype=np.int64))
+    if fortran or dtype.hasobject or not dtype.isnative or dtype.name not in _DTYPES or hbytes % dtype.itemsize \
+            or not hasattr(torch, dtype.name):
+        return host("%s, fortran_order %s" % (dtype, fortran))
+    if hbytes + count * dtype.itemsize != m['usize']:
+        raise IOError("%s: member %s holds %d bytes, its header describes %d" % (fname, key, m['usize'], hbytes + count * dtype.itemsize))
+    t = out[hbytes:].view(getattr(torch, dtype.name)).reshape(shape)
+    if stages is not None:
+        stages['path'] = 'device'
+        stages['header'] = stages.get('header', 0.0) + (time.perf_counter() - t2)
+    return t
+
+
+def peek_npy_header(fname, key):
+    """(shape, fortran_order, dtype) of member `<key>.npy` without inflating it: the first compressed bytes of the member are
+    read and only the .npy header at the head of the stream is decoded (zlib, a few hundred bytes); None where that cannot be done."""
+    import zlib
+    try:
+        m = locate_member(fname, key)
+        if m['method'] not in (0, 8) or m['flags'] & 0x1:
+            return None
+        with open(fname, 'rb') as f:
+            f.seek(m['offset'])
+            buf = f.read(min(m['csize'], 1 << 16))
+        first = buf[:4096] if m['method'] == 0 else zlib.decompressobj(-15).decompress(buf, 4096)
+        head = parse_npy_header(first)
+    except (IOError, KeyError, zlib.error):
+        return None
+    return None if head is None else head[:3]
