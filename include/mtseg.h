@@ -413,6 +413,12 @@ int mt_head_flip_accumulate(const mt_pointwise_t* p, int sample, int flipD, int 
 int mt_head_mirror_accumulate(const mt_pointwise_t* p, int sample0, int nsamples, const int32_t* flips, int nonlin, float weight,
                               const float* gauss, float* agg, float* nb, long aX, long aY, long aZ, int x0, int y0, int z0,
                               mt_stream_t stream);
+/* The kernel instance mt_head_flip_accumulate (mirror = 0) / mt_head_mirror_accumulate (mirror != 0) launches for p (profiler name,
+ * e.g. "head_mirror_accumulate_kernel<2, 2>": elements per fp32 load — 1 dwords, 2 eight-byte pairs — and the source's storage type;
+ * a 16-bit source is always <2, type>, one 16-byte load per lane).  It is decided from the source's storage type, channel stride and
+ * base address by the function the launches call, and a head the launches refuse is refused here with the same code (sample range,
+ * nonlinearity and the aggregate are not seen here).  Touches no device. */
+int mt_head_infer_kernel_name(const mt_pointwise_t* p, int mirror, char* buf, size_t n);
 /* The network batch of a group of tiles, mirror flips included, straight from the (padded) volume vol[C][X][Y][Z]:
  * out[k][C][D][H][W] = tile k at origin (x0,y0,z0) read through the reflections in `flips` (bit 0 D, bit 1 H, bit 2 W) —
  * `x = torch.flip(x, axes)` of neural_network.py:531-586 as index arithmetic.  desc: HOST array of ntiles x (x0, y0, z0, flips). */

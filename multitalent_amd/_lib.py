@@ -190,6 +190,7 @@ SIGNATURES = {
     'mt_seg_narrow': (_i, [_vp, _l, _vp, _vp, _vp]),
     'mt_head_flip_accumulate': (_i, [_P(mt_pointwise_t), _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
     'mt_head_mirror_accumulate': (_i, [_P(mt_pointwise_t), _i, _i, _vp, _i, _f, _vp, _vp, _vp, _l, _l, _l, _i, _i, _i, _vp]),
+    'mt_head_infer_kernel_name': (_i, [_P(mt_pointwise_t), _i, C.c_char_p, _sz]),
     'mt_extract_tiles': (_i, [_vp, _i, _l, _l, _l, _vp, _i, _i, _i, _i, _vp, _vp]),
     'mt_tile_accumulate': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _l, _l, _l, _i, _i, _i, _vp]),
     'mt_normalize_threshold': (_i, [_vp, _vp, _i, _l, _vp, _i, _vp, _vp]),

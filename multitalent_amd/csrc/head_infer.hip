@@ -2,6 +2,7 @@
 // (mt_head_flip_accumulate: one mirror combination into a tile accumulator; mt_head_mirror_accumulate: all combinations of a tile
 // straight into the volume aggregate).
 #include "pw_common.h"
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
 // Inference: segmentation head + nonlinearity + un-flip + accumulation in ONE kernel (neural_network.py:502-591 does
@@ -323,40 +324,58 @@ __global__ __launch_bounds__(256) void head_mirror_accumulate_kernel(const HeadM
 }
 
 // ---- entry points: one validation-and-fill and one instance pick for both kernels
-// what both kernels need of the head (p non-null) and the part of their parameters that has the same meaning in both
-template <class Params>
-static int head_infer_fill(const char* who, const mt_pointwise_t* p, int sample0, int nsamples, int nonlin, float weight, Params& P) {
+// The instance both kernels run for a source — the ONE place that decides it (the launches and mt_head_infer_kernel_name read it):
+// a 16-bit source is one 16-byte load per lane and chunk (<2, XS>; a raw 16-byte buffer load only needs dword alignment); an fp32
+// source goes by 8-byte loads where channel stride and base allow them (<2, MT_F32>), else by dwords (<1, MT_F32>)
+struct HeadInferPick { int vec, xs; };
+static HeadInferPick head_infer_pick(int dtype, int cs, const void* base) {
+  if (dtype != MT_F32) return {2, dtype};
+  return {((cs % 2) == 0 && (((uintptr_t)base) & 7) == 0) ? 2 : 1, MT_F32};
+}
+// calls f(VEC, XS) with the pick as compile-time constants
+template <class F>
+static void head_infer_instance(const HeadInferPick k, F&& f) {
+  if (k.xs == MT_F16) f(std::integral_constant<int, 2>(), std::integral_constant<int, MT_F16>());
+  else if (k.xs == MT_BF16) f(std::integral_constant<int, 2>(), std::integral_constant<int, MT_BF16>());
+  else if (k.vec == 2) f(std::integral_constant<int, 2>(), std::integral_constant<int, MT_F32>());
+  else f(std::integral_constant<int, 1>(), std::integral_constant<int, MT_F32>());
+}
+// what both kernels need of the head alone (p non-null): everything mt_head_infer_kernel_name can see
+static int head_infer_head_ok(const char* who, const mt_pointwise_t* p) {
   MT_REQUIRE(mt_dtype_ok(p->src.dtype), "%s: bad source storage type %d", who, p->src.dtype);
   MT_REQUIRE(p->src.dtype == MT_F32 || (!(p->src.cs & 1) && !(((uintptr_t)p->src.ptr) & 3)), "%s: a 16-bit source needs an even channel stride", who);
   MT_REQUIRE(p->siD == 1 && p->siH == 1 && p->siW == 1 && p->soD == 1 && p->soH == 1 && p->soW == 1 && p->Db == p->Di && p->Hb == p->Hi &&
              p->Wb == p->Wi, "%s: 1x1x1 stride-1 head only", who);
   MT_REQUIRE(p->Cout >= 1 && p->Cout <= 64 && p->src.C == p->Cin, "%s: needs 1..64 output channels", who);
+  MT_REQUIRE(mt_cdiv(p->Cin, PW_CK) * PW_CK <= PW_MAXC && (double)p->Db * p->Hb * p->Wb * p->src.cs * 4.0 < 2147483648.0, "%s: sample too large", who);
+  return MT_OK;
+}
+// the part of the kernels' parameters that has the same meaning in both
+template <class Params>
+static int head_infer_fill(const char* who, const mt_pointwise_t* p, int sample0, int nsamples, int nonlin, float weight, Params& P) {
+  if (int rc = head_infer_head_ok(who, p)) return rc;
   MT_REQUIRE(nsamples >= 1 && nsamples <= 8 && sample0 >= 0 && sample0 + nsamples <= p->N, "%s: bad sample range", who);
   MT_REQUIRE(nonlin >= 0 && nonlin <= 2, "%s: nonlin must be 0 (none), 1 (sigmoid) or 2 (softmax)", who);
   P.c = *p; P.nchunks = mt_cdiv(p->Cin, PW_CK); P.V = (long)p->Db * p->Hb * p->Wb; P.nsb = mt_cdiv(P.V, 128);
-  MT_REQUIRE(P.nchunks * PW_CK <= PW_MAXC && (double)P.V * p->src.cs * 4.0 < 2147483648.0, "%s: sample too large", who);
   P.nonlin = nonlin; P.weight = weight;
   return MT_OK;
 }
-// A 16-bit source is one 16-byte load per lane and chunk (the <2, XS> instances); an fp32 source goes by 8-byte loads where channel
-// stride and base allow them, else by dwords (<1>)
-#define HEAD_INFER_LAUNCH(KERNEL, P, stream)                                                                                          \
-  do {                                                                                                                               \
-    const mt_src_t& S_ = (P).c.src;                                                                                                  \
-    const dim3 g_((unsigned)(P).nsb);                                                                                                \
-    hipStream_t st_ = (hipStream_t)(stream);                                                                                         \
-    if (S_.dtype == MT_F16) hipLaunchKernelGGL((KERNEL<2, MT_F16>), g_, dim3(256), 0, st_, P);                                       \
-    else if (S_.dtype == MT_BF16) hipLaunchKernelGGL((KERNEL<2, MT_BF16>), g_, dim3(256), 0, st_, P);                                \
-    else if ((S_.cs % 2) == 0 && (((uintptr_t)S_.ptr) & 7) == 0) hipLaunchKernelGGL(KERNEL<2>, g_, dim3(256), 0, st_, P);            \
-    else hipLaunchKernelGGL(KERNEL<1>, g_, dim3(256), 0, st_, P);                                                                    \
-  } while (0)
+extern "C" int mt_head_infer_kernel_name(const mt_pointwise_t* p, int mirror, char* buf, size_t n) {
+  MT_REQUIRE(p != nullptr && buf != nullptr && n > 0, "head_infer_kernel_name: null pointers");
+  if (int rc = head_infer_head_ok("head_infer_kernel_name", p)) return rc;
+  const HeadInferPick k = head_infer_pick(p->src.dtype, p->src.cs, p->src.ptr);
+  snprintf(buf, n, "head_%s_accumulate_kernel<%d, %d>", mirror ? "mirror" : "flip", k.vec, k.xs);
+  return MT_OK;
+}
 extern "C" int mt_head_flip_accumulate(const mt_pointwise_t* p, int sample, int flipD, int flipH, int flipW, int nonlin, float weight,
                                        float* acc, int first, mt_stream_t stream) {
   MT_REQUIRE(p != nullptr && acc != nullptr, "head_flip_accumulate: null pointers");
   HeadAccParams P;
   if (int rc = head_infer_fill("head_flip_accumulate", p, sample, 1, nonlin, weight, P)) return rc;
   P.sample = sample; P.fD = flipD; P.fH = flipH; P.fW = flipW; P.first = first; P.acc = acc;
-  HEAD_INFER_LAUNCH(head_flip_accumulate_kernel, P, stream);
+  head_infer_instance(head_infer_pick(p->src.dtype, p->src.cs, p->src.ptr), [&](auto vec, auto xs) {
+    hipLaunchKernelGGL((head_flip_accumulate_kernel<decltype(vec)::value, decltype(xs)::value>), dim3((unsigned)P.nsb), dim3(256), 0, (hipStream_t)stream, P);
+  });
   MT_CHECK_LAUNCH("head_flip_accumulate");
   return MT_OK;
 }
@@ -370,8 +389,9 @@ extern "C" int mt_head_mirror_accumulate(const mt_pointwise_t* p, int sample0, i
   P.sample0 = sample0; P.nsamples = nsamples; P.gauss = gauss; P.agg = agg; P.nb = nb;
   for (int k = 0; k < 8; ++k) P.flips[k] = k < nsamples ? flips[k] : 0;
   P.aX = aX; P.aY = aY; P.aZ = aZ; P.x0 = x0; P.y0 = y0; P.z0 = z0;
-  HEAD_INFER_LAUNCH(head_mirror_accumulate_kernel, P, stream);
+  head_infer_instance(head_infer_pick(p->src.dtype, p->src.cs, p->src.ptr), [&](auto vec, auto xs) {
+    hipLaunchKernelGGL((head_mirror_accumulate_kernel<decltype(vec)::value, decltype(xs)::value>), dim3((unsigned)P.nsb), dim3(256), 0, (hipStream_t)stream, P);
+  });
   MT_CHECK_LAUNCH("head_mirror_accumulate");
   return MT_OK;
 }
-#undef HEAD_INFER_LAUNCH

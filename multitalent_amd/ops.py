@@ -662,6 +662,13 @@ def head_mirror_accumulate(p, sample0, flips, nonlin, weight, gauss, agg, nb, ag
                                                      origin[0], origin[1], origin[2], _stream()), 'head_mirror_accumulate')
 
 
+def head_infer_kernel_name(p, mirror):
+    """the kernel instance head_flip_accumulate (mirror False) / head_mirror_accumulate (mirror True) launches for p"""
+    buf = C.create_string_buffer(128)
+    _lib.check(_lib.load().mt_head_infer_kernel_name(C.byref(p), int(bool(mirror)), buf, 128), 'head_infer_kernel_name')
+    return buf.value.decode()
+
+
 def extract_tiles(vol, patch, tiles, out):
     """vol [C,X,Y,Z] device tensor; tiles: list of ((x0,y0,z0), (fD,fH,fW)); out [len(tiles), C, *patch] — see mt_extract_tiles."""
     _check_dev(vol, out)

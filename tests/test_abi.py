@@ -16,6 +16,7 @@ def test_library_exports_every_header_symbol():
     lib = _lib.load()
     syms = header_symbols()
     assert len(syms) >= 28
+    assert 'mt_head_infer_kernel_name' in syms and 'mt_pointwise_kernel_name' in syms
     for s in syms:
         assert hasattr(lib, s), "missing export: " + s
     assert set(_lib.SIGNATURES) == set(syms), (set(_lib.SIGNATURES) ^ set(syms))
