@@ -365,7 +365,8 @@ int mt_multitalent_hard_stats(const float* logits, int cs, const float* target, 
                               mt_stream_t stream);
 size_t mt_hard_stats_workspace(int B, int C);
 /* Softmax Dice+CE for one level (dice_loss.py:100-195,488-545; crossentropy.py:4-11):
- * stats[B][C][4] = (ce_sum (only c=0 slot used), tp, fp, fn). */
+ * stats[B][C][4] = (ce_sum (only c=0 slot used, the others 0), tp, fp, fn).  A label outside 0..C-1 is no class: a zero one-hot
+ * row, no CE term, and no CE gradient in the backward. */
 int mt_softmax_dice_ce_fwd(const float* logits, int cs, const float* target, int B, long V, int C,
                            float* stats, void* ws, size_t ws_bytes, mt_stream_t stream);
 int mt_softmax_dice_ce_bwd(const float* logits, int cs, const float* target, int B, long V, int C,
@@ -386,6 +387,19 @@ int mt_softmax_dice_ce_bwd(const float* logits, int cs, const float* target, int
 int mt_loss_combine(const float* stats, const float* dice, int dice_stride, int L, int B, int C, const float* ce_coef,
                     const float* dice_coef, int flags, int c0, float smooth_num, float smooth_den, float den_eps, float clamp_min,
                     float dice_grad_scale, float* out3, float* gstats, mt_stream_t stream);
+/* Which kernel a loss launch takes (additions to ABI 4; the launch and the query read one decision, no device is touched, and of a
+ * pointer only NULL-ness and alignment are read).  buf receives the name as a profiler prints it; a query returns what the launch
+ * returns for the arguments it sees (MT_EINVAL where the launch refuses them).
+ *   mt_multitalent_loss_fwd: "mt_loss_fwd_sparse_kernel" (cs == C) | "mt_loss_fwd_kernel".  Inside the former the body is chosen per
+ *     sample on the device: 1 <= popcount(valid[b] & mask(C)) <= 23 takes the sparse body, anything else the flat one.
+ *   mt_multitalent_loss_bwd: "mt_loss_bwd_wide_kernel" (16-byte stores: cs == dcs == C >= 2, V * C % 4 == 0, both bases 16-byte
+ *     aligned) | "mt_loss_bwd_flat_kernel" (cs == dcs == C) | "mt_loss_bwd_kernel".
+ *   mt_softmax_dice_ce_fwd / _bwd (backward != 0): "softmax_loss_fwd_kernel<4>" (C <= 4), <8>, <16> | "softmax_loss_fwd_wide_kernel".
+ * *vpb / *nblk (may be NULL): voxels per workgroup and workgroups per sample of the named kernel. */
+int mt_multitalent_loss_fwd_kernel_name(int cs, long V, int C, char* buf, size_t n, long* vpb, int* nblk);
+int mt_multitalent_loss_bwd_kernel_name(const float* logits, int cs, const float* dlogits, int dcs, long V, int C, char* buf, size_t n,
+                                        long* vpb, int* nblk);
+int mt_softmax_dice_ce_kernel_name(int C, int backward, char* buf, size_t n);
 
 /* ---- optimizer (nnUNetTrainerV2.py:166-170; clip MultiTalent_Trainer_DDP.py:352,362) --------- */
 int mt_sumsq(const float* x, long n, float* out /* [1], overwritten */, void* ws, size_t ws_bytes,

@@ -137,6 +137,9 @@ SIGNATURES = {
     'mt_softmax_dice_ce_fwd': (_i, [_vp, _i, _vp, _i, _l, _i, _vp, _vp, _sz, _vp]),
     'mt_softmax_dice_ce_bwd': (_i, [_vp, _i, _vp, _i, _l, _i, _vp, _vp, _i, _vp]),
     'mt_loss_combine': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
+    'mt_multitalent_loss_fwd_kernel_name': (_i, [_i, _l, _i, C.c_char_p, _sz, _P(C.c_long), _P(C.c_int)]),
+    'mt_multitalent_loss_bwd_kernel_name': (_i, [_vp, _i, _vp, _i, _l, _i, C.c_char_p, _sz, _P(C.c_long), _P(C.c_int)]),
+    'mt_softmax_dice_ce_kernel_name': (_i, [_i, _i, C.c_char_p, _sz]),
     'mt_sumsq': (_i, [_vp, _l, _vp, _vp, _sz, _vp]),
     'mt_sumsq_workspace': (_sz, [_l]),
     'mt_sgd_nesterov': (_i, [_vp, _vp, _vp, _l, _f, _f, _f, _i, _vp, _f, _vp]),

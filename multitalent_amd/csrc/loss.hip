@@ -326,20 +326,41 @@ extern "C" size_t mt_loss_workspace(int B, long V, int C) {
   return (size_t)B * nb * C * 4 * sizeof(float);
 }
 
+// ---- dispatch of the launchers that choose between kernels: ONE decision per launch (*_resolve), read by the launch and by its
+// mt_*_kernel_name query.  Of a pointer only NULL-ness and alignment are read, so the queries may be asked with addresses nothing
+// stands behind.  Inside mt_loss_fwd_sparse_kernel the body is chosen per sample (1 <= popcount(valid[b] & mask(C)) <= LF_SPARSE_MAX
+// takes the sparse body, anything else lf_fwd_flat_body): that is device data and not part of the decision here.
+enum { LF_STRIDED = 0, LF_FLAT = 1, LF_WIDE = 2 };            // LF_FLAT: mt_loss_fwd_sparse_kernel (forward) | mt_loss_bwd_flat_kernel
+struct LfChoice { int kind; long vpb; int nblk; };            // voxels per block, blocks per sample
+static int mt_loss_fwd_resolve(int cs, long V, int C, LfChoice& ch) {
+  MT_REQUIRE(V > 0 && C > 0 && C <= 64, "multitalent_loss_fwd: bad args (C must be <= 64)");
+  if (cs == C) ch = LfChoice{LF_FLAT, lf_vpb(lf_A(C) / C), lf_blocks(V, C)};   // contiguous logits (what the engine produces): flat coalesced kernel
+  else ch = LfChoice{LF_STRIDED, LS_VB, mt_cdiv(V, LS_VB)};
+  return MT_OK;
+}
+extern "C" int mt_multitalent_loss_fwd_kernel_name(int cs, long V, int C, char* buf, size_t n, long* vpb, int* nblk) {
+  MT_REQUIRE(buf != nullptr && n > 0, "multitalent_loss_fwd_kernel_name: no buffer");
+  LfChoice ch;
+  if (int rc = mt_loss_fwd_resolve(cs, V, C, ch)) return rc;
+  snprintf(buf, n, "%s", ch.kind == LF_FLAT ? "mt_loss_fwd_sparse_kernel" : "mt_loss_fwd_kernel");
+  if (vpb) *vpb = ch.vpb;
+  if (nblk) *nblk = ch.nblk;
+  return MT_OK;
+}
+
 extern "C" int mt_multitalent_loss_fwd(const float* logits, int cs, const float* target, int B, long V, int C,
                                        const uint64_t* valid, const uint64_t* lut, float* stats, void* ws,
                                        size_t ws_bytes, mt_stream_t stream) {
   MT_REQUIRE(logits && target && valid && lut && stats && B > 0 && V > 0 && C > 0 && C <= 64, "multitalent_loss_fwd: bad args (C must be <= 64)");
   if (ws == nullptr || ws_bytes < mt_loss_workspace(B, V, C)) { mt_set_error("multitalent_loss_fwd: workspace too small"); return MT_EWORKSPACE; }
+  LfChoice ch;
+  if (int rc = mt_loss_fwd_resolve(cs, V, C, ch)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  int nblk;
-  if (cs == C) {            // contiguous logits (what the engine produces): flat coalesced kernel
-    nblk = lf_blocks(V, C);
-    hipLaunchKernelGGL(mt_loss_fwd_sparse_kernel, dim3(nblk, B), dim3(256), 0, st, logits, target, V, C, valid, lut, nblk, lf_vpb(lf_A(C) / C), (float*)ws);
-  } else {
-    nblk = mt_cdiv(V, LS_VB);
+  const int nblk = ch.nblk;
+  if (ch.kind == LF_FLAT)
+    hipLaunchKernelGGL(mt_loss_fwd_sparse_kernel, dim3(nblk, B), dim3(256), 0, st, logits, target, V, C, valid, lut, nblk, ch.vpb, (float*)ws);
+  else
     hipLaunchKernelGGL(mt_loss_fwd_kernel, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, valid, lut, nblk, (float*)ws);
-  }
   hipLaunchKernelGGL(loss_stats_finalize_kernel, dim3(C * 4, B), dim3(64), 0, st, (const float*)ws, nblk, C, stats);
   MT_CHECK_LAUNCH("multitalent_loss_fwd");
   return MT_OK;
@@ -380,20 +401,44 @@ __global__ __launch_bounds__(256) void mt_loss_bwd_kernel(const float* __restric
   }
 }
 
+static int mt_loss_bwd_resolve(const void* logits, int cs, const void* dlogits, int dcs, long V, int C, LfChoice& ch) {
+  MT_REQUIRE(logits && dlogits && V > 0 && C > 0 && C <= 64, "multitalent_loss_bwd: bad args");
+  const long vpb = lf_vpb(lf_A(C) / C);
+  // C >= 2: the quad's channel index is unwrapped by ONE conditional subtraction (c + 3 < 2C), wrong for a single channel
+  // ((vpb * C) & 3 never holds: vpb is LF_KMAX * nsub or LF_VMAX, both multiples of four; kept as the kernel's stated precondition)
+  if (cs == C && dcs == C && C >= 2 && ((V * C) & 3) == 0 && ((vpb * C) & 3) == 0 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0)
+    ch = LfChoice{LF_WIDE, vpb, lf_blocks(V, C)};
+  else if (cs == C && dcs == C)
+    ch = LfChoice{LF_FLAT, vpb, lf_blocks(V, C)};
+  else
+    ch = LfChoice{LF_STRIDED, LS_VB, mt_cdiv(V, LS_VB)};
+  return MT_OK;
+}
+extern "C" int mt_multitalent_loss_bwd_kernel_name(const float* logits, int cs, const float* dlogits, int dcs, long V, int C,
+                                                   char* buf, size_t n, long* vpb, int* nblk) {
+  MT_REQUIRE(buf != nullptr && n > 0, "multitalent_loss_bwd_kernel_name: no buffer");
+  LfChoice ch;
+  if (int rc = mt_loss_bwd_resolve(logits, cs, dlogits, dcs, V, C, ch)) return rc;
+  snprintf(buf, n, "%s", ch.kind == LF_WIDE ? "mt_loss_bwd_wide_kernel" : ch.kind == LF_FLAT ? "mt_loss_bwd_flat_kernel" : "mt_loss_bwd_kernel");
+  if (vpb) *vpb = ch.vpb;
+  if (nblk) *nblk = ch.nblk;
+  return MT_OK;
+}
+
 extern "C" int mt_multitalent_loss_bwd(const float* logits, int cs, const float* target, int B, long V, int C,
                                        const uint64_t* valid, const uint64_t* lut, const float* gstats,
                                        float* dlogits, int dcs, mt_stream_t stream) {
   MT_REQUIRE(logits && target && valid && lut && gstats && dlogits && B > 0 && V > 0 && C > 0 && C <= 64, "multitalent_loss_bwd: bad args");
-  const long vpb = lf_vpb(lf_A(C) / C);
-  // C >= 2: the quad's channel index is unwrapped by ONE conditional subtraction (c + 3 < 2C), wrong for a single channel
-  if (cs == C && dcs == C && C >= 2 && ((V * C) & 3) == 0 && ((vpb * C) & 3) == 0 && (((uintptr_t)logits | (uintptr_t)dlogits) & 15) == 0)
-    hipLaunchKernelGGL(mt_loss_bwd_wide_kernel, dim3(lf_blocks(V, C), B), dim3(256), 0, (hipStream_t)stream, logits, target, V, C, valid, lut,
-                       gstats, vpb, dlogits);
-  else if (cs == C && dcs == C)
-    hipLaunchKernelGGL(mt_loss_bwd_flat_kernel, dim3(lf_blocks(V, C), B), dim3(256), 0, (hipStream_t)stream, logits, target, V, C, valid, lut,
+  LfChoice ch;
+  if (int rc = mt_loss_bwd_resolve(logits, cs, dlogits, dcs, V, C, ch)) return rc;
+  if (ch.kind == LF_WIDE)
+    hipLaunchKernelGGL(mt_loss_bwd_wide_kernel, dim3(ch.nblk, B), dim3(256), 0, (hipStream_t)stream, logits, target, V, C, valid, lut,
+                       gstats, ch.vpb, dlogits);
+  else if (ch.kind == LF_FLAT)
+    hipLaunchKernelGGL(mt_loss_bwd_flat_kernel, dim3(ch.nblk, B), dim3(256), 0, (hipStream_t)stream, logits, target, V, C, valid, lut,
                        gstats, lf_A(C), dlogits);
   else
-    hipLaunchKernelGGL(mt_loss_bwd_kernel, dim3(mt_cdiv(V, LS_VB), B), dim3(256), 0, (hipStream_t)stream, logits, cs, target, V, C,
+    hipLaunchKernelGGL(mt_loss_bwd_kernel, dim3(ch.nblk, B), dim3(256), 0, (hipStream_t)stream, logits, cs, target, V, C,
                        valid, lut, gstats, dlogits, dcs);
   MT_CHECK_LAUNCH("multitalent_loss_bwd");
   return MT_OK;
@@ -478,9 +523,13 @@ __global__ __launch_bounds__(256) void softmax_loss_fwd_kernel(const float* __re
     float x[MAXC], mx = -3.0e38f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) { x[c] = (c < C) ? logits[e * cs + c] : -3.0e38f; mx = fmaxf(mx, x[c]); }
-    float se = 0.f;
+    float se = 0.f, xl = 0.f;                                      // xl: the label's logit minus the maximum
 #pragma unroll
-    for (int c = 0; c < MAXC; ++c) { x[c] = (c < C) ? __expf(x[c] - mx) : 0.f; se += x[c]; }
+    for (int c = 0; c < MAXC; ++c) {
+      const float d = x[c] - mx;
+      if (c < C && lab == c) xl = d;
+      x[c] = (c < C) ? __expf(d) : 0.f; se += x[c];
+    }
     const float inv = 1.f / se;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
@@ -488,9 +537,10 @@ __global__ __launch_bounds__(256) void softmax_loss_fwd_kernel(const float* __re
         const float p = x[c] * inv;
         const float y = (lab == c) ? 1.f : 0.f;
         tp[c] += p * y; fp[c] += p * (1.f - y); fn[c] += (1.f - p) * y;
-        if (lab == c) ce -= __logf(fmaxf(p, 1e-38f));
       }
     }
+    // -log_softmax of the label's class as log(sum) - (x - max): -log(p) is lost once p underflows (a logit 88 below the maximum)
+    if (lab >= 0 && lab < C) ce += __logf(se) - xl;
   }
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) { tp[c] = mt_wave_sum(tp[c]); fp[c] = mt_wave_sum(fp[c]); fn[c] = mt_wave_sum(fn[c]); }
@@ -535,11 +585,12 @@ __global__ __launch_bounds__(256) void softmax_loss_fwd_wide_kernel(const float*
     const float x = act ? logits[e * cs + lane] : -3.0e38f;
     const float mx = mt_wave_max(x);
     const float ex = act ? __expf(x - mx) : 0.f;
-    const float p = ex / mt_wave_sum(ex);
+    const float se = mt_wave_sum(ex);
+    const float p = ex / se;
     if (act) {
       const float y = (lab == lane) ? 1.f : 0.f;
       tp += p * y; fp += p * (1.f - y); fn += (1.f - p) * y;
-      if (lab == lane) ce -= __logf(fmaxf(p, 1e-38f));
+      if (lab == lane) ce += __logf(se) - (x - mx);                // log(sum) - (x - max): see softmax_loss_fwd_kernel
     }
   }
   ce = mt_wave_sum(ce);
@@ -555,15 +606,33 @@ __global__ __launch_bounds__(256) void softmax_loss_fwd_wide_kernel(const float*
   }
 }
 
+// MAXC of the register kernels (softmax_loss_fwd_kernel / _bwd_kernel<MAXC>: one thread per voxel), 0 = the wave-per-voxel kernels
+static int softmax_loss_resolve(int C, int backward, int& maxc) {
+  if (backward) MT_REQUIRE(C > 1 && C <= 64, "softmax_dice_ce_bwd: bad args (2 <= C <= 64)");
+  else MT_REQUIRE(C > 1 && C <= 64, "softmax_dice_ce_fwd: bad args (2 <= C <= 64)");
+  maxc = C <= 4 ? 4 : C <= 8 ? 8 : C <= 16 ? 16 : 0;
+  return MT_OK;
+}
+extern "C" int mt_softmax_dice_ce_kernel_name(int C, int backward, char* buf, size_t n) {
+  MT_REQUIRE(buf != nullptr && n > 0, "softmax_dice_ce_kernel_name: no buffer");
+  int maxc;
+  if (int rc = softmax_loss_resolve(C, backward, maxc)) return rc;
+  if (maxc > 0) snprintf(buf, n, "softmax_loss_%s_kernel<%d>", backward ? "bwd" : "fwd", maxc);
+  else snprintf(buf, n, "softmax_loss_%s_wide_kernel", backward ? "bwd" : "fwd");
+  return MT_OK;
+}
+
 extern "C" int mt_softmax_dice_ce_fwd(const float* logits, int cs, const float* target, int B, long V, int C,
                                       float* stats, void* ws, size_t ws_bytes, mt_stream_t stream) {
   MT_REQUIRE(logits && target && stats && B > 0 && V > 0 && C > 1 && C <= 64, "softmax_dice_ce_fwd: bad args (2 <= C <= 64)");
   if (ws == nullptr || ws_bytes < mt_loss_workspace(B, V, C)) { mt_set_error("softmax_dice_ce_fwd: workspace too small"); return MT_EWORKSPACE; }
+  int maxc;
+  if (int rc = softmax_loss_resolve(C, 0, maxc)) return rc;
   const int nblk = mt_cdiv(V, LS_VB);
   hipStream_t st = (hipStream_t)stream;
-  if (C <= 4) hipLaunchKernelGGL(softmax_loss_fwd_kernel<4>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
-  else if (C <= 8) hipLaunchKernelGGL(softmax_loss_fwd_kernel<8>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
-  else if (C <= 16) hipLaunchKernelGGL(softmax_loss_fwd_kernel<16>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
+  if (maxc == 4) hipLaunchKernelGGL(softmax_loss_fwd_kernel<4>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
+  else if (maxc == 8) hipLaunchKernelGGL(softmax_loss_fwd_kernel<8>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
+  else if (maxc == 16) hipLaunchKernelGGL(softmax_loss_fwd_kernel<16>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
   else hipLaunchKernelGGL(softmax_loss_fwd_wide_kernel, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, nblk, (float*)ws);
   hipLaunchKernelGGL(loss_stats_finalize_kernel, dim3(C * 4, B), dim3(64), 0, st, (const float*)ws, nblk, C, stats);
   MT_CHECK_LAUNCH("softmax_dice_ce_fwd");
@@ -595,6 +664,7 @@ __global__ __launch_bounds__(256) void softmax_loss_bwd_kernel(const float* __re
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) { x[c] = (c < C) ? __expf(x[c] - mx) : 0.f; se += x[c]; }
     const float inv = 1.f / se;
+    const float cek = (lab >= 0 && lab < C) ? ce_coef : 0.f;      // a label that is no class has no CE term in the forward
     float G[MAXC], dot = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
@@ -608,7 +678,7 @@ __global__ __launch_bounds__(256) void softmax_loss_bwd_kernel(const float* __re
     for (int c = 0; c < MAXC; ++c) {
       if (c < C) {
         const float y = (lab == c) ? 1.f : 0.f;
-        dlogits[e * dcs + c] = ce_coef * (x[c] - y) + x[c] * (G[c] - dot);
+        dlogits[e * dcs + c] = cek * (x[c] - y) + x[c] * (G[c] - dot);
       }
     }
   }
@@ -637,18 +707,21 @@ __global__ __launch_bounds__(256) void softmax_loss_bwd_wide_kernel(const float*
     const float y = (lab == lane) ? 1.f : 0.f;
     const float G = y * (a_tp - a_fn) + (1.f - y) * a_fp;
     const float dot = mt_wave_sum(p * G);
-    if (act) dlogits[e * dcs + lane] = ce_coef * (p - y) + p * (G - dot);
+    const float cek = (lab >= 0 && lab < C) ? ce_coef : 0.f;      // a label that is no class has no CE term in the forward
+    if (act) dlogits[e * dcs + lane] = cek * (p - y) + p * (G - dot);
   }
 }
 
 extern "C" int mt_softmax_dice_ce_bwd(const float* logits, int cs, const float* target, int B, long V, int C,
                                       const float* gstats, float* dlogits, int dcs, mt_stream_t stream) {
   MT_REQUIRE(logits && target && gstats && dlogits && B > 0 && V > 0 && C > 1 && C <= 64, "softmax_dice_ce_bwd: bad args (2 <= C <= 64)");
+  int maxc;
+  if (int rc = softmax_loss_resolve(C, 1, maxc)) return rc;
   const int nblk = mt_cdiv(V, LS_VB);
   hipStream_t st = (hipStream_t)stream;
-  if (C <= 4) hipLaunchKernelGGL(softmax_loss_bwd_kernel<4>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
-  else if (C <= 8) hipLaunchKernelGGL(softmax_loss_bwd_kernel<8>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
-  else if (C <= 16) hipLaunchKernelGGL(softmax_loss_bwd_kernel<16>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
+  if (maxc == 4) hipLaunchKernelGGL(softmax_loss_bwd_kernel<4>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
+  else if (maxc == 8) hipLaunchKernelGGL(softmax_loss_bwd_kernel<8>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
+  else if (maxc == 16) hipLaunchKernelGGL(softmax_loss_bwd_kernel<16>, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
   else hipLaunchKernelGGL(softmax_loss_bwd_wide_kernel, dim3(nblk, B), dim3(256), 0, st, logits, cs, target, V, C, gstats, dlogits, dcs);
   MT_CHECK_LAUNCH("softmax_dice_ce_bwd");
   return MT_OK;

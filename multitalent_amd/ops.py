@@ -629,6 +629,30 @@ def loss_combine(stats, dice, dice_stride, ce_coef, dice_coef, flags, c0, smooth
                                            float(clamp_min), float(dice_grad_scale), _ptr(out3), _ptr(gstats), _stream()), 'loss_combine')
 
 
+def multitalent_loss_fwd_kernel_name(cs, V, Cn):
+    """(kernel multitalent_loss_fwd launches for logits of channel stride cs, voxels per workgroup, workgroups per sample)"""
+    buf, vpb, nblk = C.create_string_buffer(128), C.c_long(0), C.c_int(0)
+    _lib.check(_lib.load().mt_multitalent_loss_fwd_kernel_name(int(cs), int(V), int(Cn), buf, 128, C.byref(vpb), C.byref(nblk)),
+               'multitalent_loss_fwd_kernel_name')
+    return buf.value.decode(), vpb.value, nblk.value
+
+
+def multitalent_loss_bwd_kernel_name(logits, cs, dlogits, dcs, V, Cn):
+    """the same for multitalent_loss_bwd; logits / dlogits: base ADDRESSES (only their alignment is read)"""
+    buf, vpb, nblk = C.create_string_buffer(128), C.c_long(0), C.c_int(0)
+    _lib.check(_lib.load().mt_multitalent_loss_bwd_kernel_name(C.c_void_p(int(logits)), int(cs), C.c_void_p(int(dlogits)), int(dcs), int(V),
+                                                               int(Cn), buf, 128, C.byref(vpb), C.byref(nblk)),
+               'multitalent_loss_bwd_kernel_name')
+    return buf.value.decode(), vpb.value, nblk.value
+
+
+def softmax_dice_ce_kernel_name(Cn, backward):
+    """the kernel instance softmax_dice_ce_fwd (backward False) / _bwd (True) launches for Cn classes"""
+    buf = C.create_string_buffer(128)
+    _lib.check(_lib.load().mt_softmax_dice_ce_kernel_name(int(Cn), int(bool(backward)), buf, 128), 'softmax_dice_ce_kernel_name')
+    return buf.value.decode()
+
+
 def sumsq(x, out, ws):
     _lib.check(_lib.load().mt_sumsq(_ptr(x), x.numel(), _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), _stream()), 'sumsq')
 

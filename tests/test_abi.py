@@ -17,6 +17,7 @@ def test_library_exports_every_header_symbol():
     syms = header_symbols()
     assert len(syms) >= 28
     assert 'mt_head_infer_kernel_name' in syms and 'mt_pointwise_kernel_name' in syms
+    assert {'mt_multitalent_loss_fwd_kernel_name', 'mt_multitalent_loss_bwd_kernel_name', 'mt_softmax_dice_ce_kernel_name'} <= set(syms)
     for s in syms:
         assert hasattr(lib, s), "missing export: " + s
     assert set(_lib.SIGNATURES) == set(syms), (set(_lib.SIGNATURES) ^ set(syms))
