@@ -596,6 +596,42 @@ int mt_inflate_scan(const uint8_t* comp, long n_comp, long unit_limit, int final
 int mt_inflate_write(const uint8_t* comp, long n_comp, void* ws, size_t ws_bytes, int n_units, int n_spans, uint8_t* out,
                      long n_out, mt_stream_t stream);
 int mt_inflate_crc(const uint8_t* data, long n, int piece, uint32_t* crcs, mt_stream_t stream);
+/* INFLATE of a raw DEFLATE stream WITHOUT restart points (a file of another writer: zlib, numpy, gzip, pigz), parallel over block
+ * starts that are found by search (csrc/inflate_spec.hip).  comp[0, n_comp) in DEVICE memory, any alignment, 1 ..
+ * INT32_MAX - 64 bytes; chunk: a power of two in 64 .. 2^20.  Positions are BIT positions (64-bit).  A UNIT starts at a candidate,
+ * decodes consecutive blocks and ends at the first block end that is a candidate's position, or at a block with BFINAL (the stream
+ * ends at the next byte boundary).  Its matches may reach up to 32768 bytes in front of it.
+ * mt_inflate_spec_scan: candidates are bit 0 and, for every chunk of `chunk` compressed bytes, the first bit position p > 0 in the
+ *   chunk at which the header of a non-final dynamic block is accepted as zlib's inflate accepts one (HLIT <= 29, HDIST <= 29, a
+ *   complete code-length code, a valid length sequence with a length for symbol 256, neither code over-subscribed and each complete
+ *   unless its longest code is one bit, no header bit behind the input); the header may extend past the chunk.  Every candidate is
+ *   decoded without output by one wave: more than unit_limit (1 .. 2^30) output bytes or more than span_limit (>= 1) consumed
+ *   compressed bytes is TOO_LONG, an invalid block or code or a read behind the input BAD, a match in front of bit 0 CORRUPT.  One
+ *   wave then follows end -> start from bit 0: a candidate on the way that failed gives the stream its status, a last unit without
+ *   BFINAL or one that does not end at n_comp CORRUPT, n_expect >= 0 and another total SIZE.  Candidates that are not reached
+ *   are ignored, so the result never depends on what the search accepts.  steps: a mask of 1 search, 2 size pass, 4 chain (7: all;
+ *   the parts exist so that a caller can time them, each needs the ones in front of it in the same ws).
+ *   ws (DEVICE, 16-byte aligned, mt_inflate_spec_workspace(n_comp, chunk) bytes: 60 per chunk) begins with { int32 status; int32
+ *   n_units; int64 total; int32 n_cand; int32 n_spans; int32 max_reach; uint32 shortest_unit; }: the statuses of mt_inflate_scan;
+ *   max_reach = the farthest a match of a chained unit reaches in front of its unit, shortest_unit = the fewest bytes of one.
+ *   mt_inflate_spec_workspace_part: part 0 = byte offset of the candidates' bit positions (int64, ascending), 1 = byte offset of
+ *   the chain (int32 index into the candidates, one per unit), 2 = entries of either table; 0 for other arguments.
+ * mt_inflate_spec_write: the same comp, chunk and ws after a scan with status OK, its n_units, n_spans and n_out == total, and ws2
+ *   (DEVICE, 16-byte aligned, mt_inflate_spec_write_workspace(n_units, n_spans, n_out) bytes: 2 per output byte, 32768 per unit,
+ *   16 per stored block).  steps: a mask of 1 symbols (the non-empty stored blocks are copied by the whole grid, then one wave per
+ *   unit decodes into 16-bit symbols: a byte, or 0x8000 | index into the 32768 bytes in front of the unit), 2 windows (one
+ *   workgroup resolves every unit's last 32768 bytes in order), 4 resolve (out[i] from its symbol and the window in front of its
+ *   unit, 16-byte stores).  A marker that points in front of the stream sets the head's status to CORRUPT, which the caller reads
+ *   after the call; out then holds zeros there.  The values are checked against the head on the device: a mismatch writes nothing.
+ * Errors as for mt_inflate_*: MT_EINVAL / MT_EWORKSPACE before any launch, the stream's verdict is a status.  Nothing is
+ *   synchronised, there is no process-wide state. */
+size_t mt_inflate_spec_workspace(long n_comp, int chunk);
+size_t mt_inflate_spec_workspace_part(long n_comp, int chunk, int part);
+size_t mt_inflate_spec_write_workspace(int n_units, int n_spans, long n_out);
+int mt_inflate_spec_scan(const uint8_t* comp, long n_comp, int chunk, long unit_limit, long span_limit, long n_expect, int steps,
+                         void* ws, size_t ws_bytes, mt_stream_t stream);
+int mt_inflate_spec_write(const uint8_t* comp, long n_comp, int chunk, void* ws, size_t ws_bytes, int n_units, int n_spans, void* ws2,
+                          size_t ws2_bytes, uint8_t* out, long n_out, int steps, mt_stream_t stream);
 /* Connected-component post-processing (remove_all_but_the_largest_connected_component, postprocessing/connected_components.py:48-101).
  * mt_cc_label3d: `lmap, num_objects = scipy.ndimage.label(mask)` (:76) with scipy's default 3-D structure, 6-connectivity (face
  * neighbours only), on the mask {v : member[seg[v]] != 0} of a contiguous uint8 volume seg[D, H, W].  member: HOST array of 256

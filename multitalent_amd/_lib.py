@@ -161,6 +161,11 @@ SIGNATURES = {
     'mt_inflate_scan': (_i, [_vp, _l, _l, _i, _l, _vp, _sz, _vp]),
     'mt_inflate_write': (_i, [_vp, _l, _vp, _sz, _i, _i, _vp, _l, _vp]),
     'mt_inflate_crc': (_i, [_vp, _l, _i, _vp, _vp]),
+    'mt_inflate_spec_workspace': (_sz, [_l, _i]),
+    'mt_inflate_spec_workspace_part': (_sz, [_l, _i, _i]),
+    'mt_inflate_spec_write_workspace': (_sz, [_i, _i, _l]),
+    'mt_inflate_spec_scan': (_i, [_vp, _l, _i, _l, _l, _l, _i, _vp, _sz, _vp]),
+    'mt_inflate_spec_write': (_i, [_vp, _l, _i, _vp, _sz, _i, _i, _vp, _sz, _vp, _l, _i, _vp]),
     'mt_cc_label3d': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'mt_cc_remove': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _d, _i, _d, _vp, _vp]),
     'mt_nonzero_mask': (_i, [_vp, _i, _l, _vp, _vp]),

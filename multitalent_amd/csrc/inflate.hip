@@ -14,15 +14,13 @@
 //                     every match nearer than IF_RB - 258 bytes, and leaves in 16-byte stores.
 //   mt_inflate_crc    CRC-32 of fixed-size pieces of the result; the host joins them.
 // Decoding is wave-uniform: every lane holds the same bit buffer (fed from a 256-byte window of the input that the lanes hold one
-// dword each), the lanes share table construction, match copies and the stores.  Restated in tests/inflate_host.py.
-#include "stream_common.h"
+// dword each), the lanes share table construction, match copies and the stores.  Restated in tests/inflate_host.py.  The tables,
+// the bit reader and the reading of a block's two codes live in inflate_common.h / inflate_codes.inc, shared with inflate_spec.hip.
+#include "inflate_common.h"
 #include "crc32_common.h"
 
-#define IF_WAVE 64
 #define IF_RB 4096                                   // ring bytes (a power of two)
 #define IF_FLUSH 2048                                // unflushed bytes at which the ring is written out; IF_FLUSH + 258 <= IF_RB
-#define IF_FASTL 10                                  // bits that index the literal/length table; longer codes walk the counts
-#define IF_FASTD 8
 #define IF_SCAN_THREADS 256
 #define IF_SCAN_PER 16
 #define IF_SCAN_TILE (IF_SCAN_THREADS * IF_SCAN_PER)
@@ -31,7 +29,6 @@
 #define IF_HEAD_BYTES 64
 #define IF_MAX_UNIT_LIMIT (1l << 30)
 
-enum { IF_OK = 0, IF_FOREIGN = 1, IF_TOO_LONG = 2, IF_BAD = 3, IF_CORRUPT = 4, IF_SIZE = 5 };
 enum { IF_MODE_SIZE = 0, IF_MODE_SPANS = 1, IF_MODE_WRITE = 2 };
 
 struct IfHead { int32_t status, n_units; int64_t total; int32_t n_cand, n_spans; };
@@ -124,95 +121,9 @@ __global__ __launch_bounds__(IF_SCAN_THREADS) void inflate_cand_write_kernel(con
 }
 
 // ------------------------------------------------------------------------------------------------ one unit
-struct IfTables {
-  uint16_t fastl[1 << IF_FASTL];    // low bits of the stream -> symbol | code length << 9; 0: a longer code (or none)
-  uint16_t fastd[1 << IF_FASTD];
-  uint16_t syml[288], symd[32], symc[20];          // symbols ordered by (code length, symbol)
-  uint16_t cntl[16], cntd[16], cntc[16], offs[16]; // codes of each length
-  uint8_t lens[320];
-  int ok;
-};
 struct IfSharedSize { IfTables T; };
 struct IfSharedWrite { uint8_t ring[IF_RB] __attribute__((aligned(16))); IfTables T; };
 
-__device__ static const uint8_t IF_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-
-// canonical decoding of the code whose bits arrive lowest first in v: -> symbol (its length in len), -1 when no code of at most
-// maxlen bits matches
-__device__ __forceinline__ int if_walk(const uint16_t* cnt, const uint16_t* sym, uint64_t v, int maxlen, int& len) {
-  int code = 0, first = 0, index = 0;
-  for (int l = 1; l <= maxlen; ++l) {
-    code |= (int)(v & 1u);
-    v >>= 1;
-    const int c = cnt[l];
-    if (code - c < first) { len = l; return sym[index + (code - first)]; }
-    index += c; first += c; first <<= 1; code <<= 1;
-  }
-  len = 0;
-  return -1;
-}
-
-// lens[0, n) -> cnt, sym and (fastbits > 0) the table; false when the lengths are over-subscribed.  All lanes call it.
-__device__ __forceinline__ bool if_build(IfTables& T, const uint8_t* lens, int n, uint16_t* cnt, uint16_t* sym, uint16_t* fast,
-                                         int fastbits, int lane) {
-  __syncthreads();
-  if (lane == 0) {
-    for (int l = 0; l < 16; ++l) cnt[l] = 0;
-    for (int s = 0; s < n; ++s) ++cnt[lens[s] & 15];
-    int left = 1, o = 0;
-    bool ok = true;
-    for (int l = 1; l < 16; ++l) { left = (left << 1) - cnt[l]; if (left < 0) { ok = false; break; } }
-    for (int l = 1; l < 16; ++l) { T.offs[l] = (uint16_t)o; o += cnt[l]; }
-    if (ok)
-      for (int s = 0; s < n; ++s) { const int l = lens[s] & 15; if (l) sym[T.offs[l]++] = (uint16_t)s; }
-    T.ok = ok ? 1 : 0;
-  }
-  __syncthreads();
-  const bool ok = T.ok != 0;
-  if (ok && fastbits)
-    for (int e = lane; e < (1 << fastbits); e += IF_WAVE) {
-      int len;
-      const int s = if_walk(cnt, sym, (uint64_t)e, fastbits, len);
-      fast[e] = s < 0 ? (uint16_t)0 : (uint16_t)(s | (len << 9));
-    }
-  __syncthreads();
-  return ok;
-}
-
-// The input as every lane sees it: a bit buffer of up to 64 bits in front of byte `ip`; bytes behind the end read as zero and
-// `used()` tells when they were consumed.
-struct IfIn {
-  const uint8_t* in; long n, ip, wbase; uint64_t bb; int nb, lane; uint32_t w;
-  __device__ __forceinline__ void open(const uint8_t* p, long n_, long at, int lane_) {
-    in = p; n = n_; ip = at; bb = 0; nb = 0; lane = lane_; w = 0; wbase = -(1l << 40);
-  }
-  __device__ __forceinline__ void window(long at) {                   // 64 aligned dwords from the one that holds byte `at`
-    wbase = at - (long)(((uintptr_t)in + (uintptr_t)at) & 3);
-    const long p = wbase + 4 * lane;
-    uint32_t v = 0;
-    if (p >= 0 && p + 4 <= n) v = *(const uint32_t*)(in + p);
-    else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) if (p + k >= 0 && p + k < n) v |= (uint32_t)in[p + k] << (8 * k);
-    }
-    w = v;
-  }
-  __device__ __forceinline__ uint32_t word32(long at) {
-    if (at >= n) return 0;
-    long a = at - wbase;
-    if (a < 0 || a + 8 > 4 * IF_WAVE) { window(at); a = at - wbase; }
-    const int i = (int)(a >> 2), sh = (int)(a & 3) * 8;
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)w, i), hi = (uint32_t)__builtin_amdgcn_readlane((int)w, i + 1);
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
-  }
-  __device__ __forceinline__ void refill() { if (nb <= 32) { bb |= (uint64_t)word32(ip) << nb; ip += 4; nb += 32; } }
-  __device__ __forceinline__ uint32_t take(int k) { const uint32_t v = (uint32_t)bb & ((1u << k) - 1u); bb >>= k; nb -= k; return v; }
-  __device__ __forceinline__ uint32_t get(int k) { refill(); return take(k); }                  // k <= 16
-  __device__ __forceinline__ void align() { const int k = nb & 7; bb >>= k; nb -= k; }
-  __device__ __forceinline__ long byte_pos() const { return ip - (nb >> 3); }                   // after align()
-  __device__ __forceinline__ void seek(long at) { ip = at; bb = 0; nb = 0; }
-  __device__ __forceinline__ bool overrun() const { return 8 * ip - nb > 8 * n; }
-};
 
 // The ring of a unit that is written: position q of the unit's output lives in ring[(bias + q) & (IF_RB - 1)], bias = the low bits
 // of its global address, so that 16-byte pieces of the ring are 16-byte pieces of memory.
@@ -288,51 +199,7 @@ __device__ __forceinline__ IfRes if_unit(IfTables& T, uint8_t* ring, const uint8
       if (final) { end = data + len; break; }
       continue;
     }
-    // ---- the two codes
-    int hlit = 288, hdist = 30;
-    if (type == 1) {
-      __syncthreads();
-      for (int s = lane; s < 320; s += IF_WAVE) T.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5);
-    } else {
-      hlit = (int)I.get(5) + 257;
-      hdist = (int)I.get(5) + 1;
-      const int hclen = (int)I.get(4) + 4;
-      if (hlit > 286 || hdist > 30) { status = IF_BAD; break; }
-      __syncthreads();
-      if (lane < 19) T.lens[lane] = 0;
-      __syncthreads();
-      for (int k = 0; k < hclen; ++k) { const uint32_t v = I.get(3); if (lane == 0) T.lens[IF_ORDER[k]] = (uint8_t)v; }
-      if (I.overrun() || !if_build(T, T.lens, 19, T.cntc, T.symc, nullptr, 0, lane)) { status = IF_BAD; break; }
-      int i = 0, prev = 0;
-      const int total = hlit + hdist;
-      while (i < total) {
-        I.refill();
-        int len;
-        const int s = __builtin_amdgcn_readfirstlane(if_walk(T.cntc, T.symc, I.bb, 7, len));
-        len = __builtin_amdgcn_readfirstlane(len);
-        if (s < 0) { status = IF_BAD; break; }
-        I.take(len);
-        if (s < 16) {
-          if (lane == 0) T.lens[i] = (uint8_t)s;
-          ++i; prev = s;
-        } else {
-          int rep, val = 0;
-          if (s == 16) { if (i == 0) { status = IF_BAD; break; } val = prev; rep = 3 + (int)I.get(2); }
-          else if (s == 17) rep = 3 + (int)I.get(3);
-          else rep = 11 + (int)I.get(7);
-          if (i + rep > total) { status = IF_BAD; break; }
-          for (int k = lane; k < rep; k += IF_WAVE) T.lens[i + k] = (uint8_t)val;
-          i += rep; prev = val;
-        }
-        if (I.overrun()) { status = IF_BAD; break; }
-      }
-      if (status != IF_OK) break;
-      __syncthreads();
-      if (T.lens[256] == 0) { status = IF_BAD; break; }
-    }
-    const bool okl = if_build(T, T.lens, hlit, T.cntl, T.syml, T.fastl, IF_FASTL, lane);
-    const bool okd = if_build(T, T.lens + hlit, hdist, T.cntd, T.symd, T.fastd, IF_FASTD, lane);
-    if (!okl || !okd) { status = IF_BAD; break; }
+#include "inflate_codes.inc"
     // ---- tokens
     for (;;) {
       I.refill();

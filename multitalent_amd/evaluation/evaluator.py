@@ -17,7 +17,7 @@ from datetime import datetime
 
 import numpy as np
 
-from ..utilities.nifti_io import read_image
+from ..utilities.nifti_io import read_image, read_image_device
 
 DEFAULT_METRICS = ["False Positive Rate", "Dice", "Jaccard", "Precision", "Recall", "Accuracy", "False Omission Rate",
                    "Negative Predictive Value", "False Negative Rate", "True Negative Rate", "False Discovery Rate",
@@ -186,8 +186,13 @@ def _surface_metrics(t, r, members, counts, names, voxel_spacing, connectivity):
 
 
 def _load(x):
-    """-> (volume: numpy array or device tensor, file name or None, spacing (x, y, z) of a file or None)."""
+    """-> (volume: numpy array or device tensor, file name or None, spacing (x, y, z) of a file or None).  With a HIP device a
+    `.nii.gz` file is read through `read_image_device`: ground-truth label maps are inflated where they are compared."""
     if isinstance(x, str):
+        import torch
+        if torch.cuda.is_available() and x.endswith('.nii.gz'):
+            vox, spacing, _, _ = read_image_device(x, torch.device('cuda', torch.cuda.current_device()))
+            return vox, x, spacing
         img = read_image(x)
         return np.asarray(img.array), x, img.spacing
     if _is_device_tensor(x):

@@ -1594,5 +1594,99 @@ def inflate_raw(comp, n_out=None, unit_limit=INFLATE_UNIT_LIMIT, final=True, sta
     return out, crc, info
 
 
+INFLATE_SPEC_CHUNK = 4096                # compressed bytes per searched chunk (measured among 2 .. 64 KiB: DESIGN 6ab)
+INFLATE_SPEC_MIN_OUT = 64 << 20          # expected output bytes from which the readers try inflate_stream (measured: DESIGN 6ab)
+INFLATE_SPEC_SPAN_CHUNKS = 64            # a unit that consumes more chunks than this found no block starts: the host reads the file
+INFLATE_SPEC_UNIT_LIMIT = 1 << 30
+_SPEC_SCAN_STEPS = (('search', 1), ('size', 2), ('chain', 4))
+_SPEC_WRITE_STEPS = (('symbols', 1), ('windows', 2), ('resolve', 4))
+
+
+def inflate_stream(comp, n_out=None, chunk=INFLATE_SPEC_CHUNK, unit_limit=INFLATE_SPEC_UNIT_LIMIT, span_limit=None, stages=None,
+                   want_starts=False):
+    """comp: uint8 device tensor (1-D, contiguous, any alignment) holding one raw DEFLATE stream of ANY writer -> (uint8 device tensor
+    of the decoded bytes, their CRC-32, info).  The stream is decoded in parallel from block starts that are searched in it
+    (mt_inflate_spec_scan / mt_inflate_spec_write): bit 0 and, per `chunk` compressed bytes (a power of two, 64 .. 2^20), the first
+    position at which a non-final dynamic block header is accepted.  n_out: the size the caller expects (another size is an IOError).
+    A unit of more than `unit_limit` output bytes or `span_limit` compressed bytes (default: 64 chunks; a stream whose block starts
+    are not found, such as a Z_FIXED one) raises InflateForeign, a malformed stream IOError, each with e.info.
+    info: {'status', 'units', 'candidates', 'spans', 'bytes', 'shortest_unit', 'max_reach'} and, with want_starts, 'positions' and
+    'starts': the bit positions of the candidates and of the units as device tensors.  stages (a dict) makes the call synchronise
+    between its passes and receives the seconds of 'search', 'size', 'chain', 'symbols', 'windows', 'resolve' and 'crc'."""
+    import time
+    from .utilities import deflate_host as H
+    _require_device(_READ, comp)
+    if comp.dtype != torch.uint8 or comp.dim() != 1 or not comp.is_contiguous():
+        raise ValueError("inflate_stream: a contiguous 1-D uint8 device tensor is expected, got %s %s" % (comp.dtype, tuple(comp.shape)))
+    n, chunk = int(comp.numel()), int(chunk)
+    span_limit = INFLATE_SPEC_SPAN_CHUNKS * chunk if span_limit is None else int(span_limit)
+    lib = _lib.load()
+
+    def timed(steps, call):
+        """one call for all steps, or one per step with a synchronise behind it when the stages are wanted"""
+        if stages is None:
+            return call(sum(m for _, m in steps))
+        for name, mask in steps:
+            t = time.perf_counter()
+            call(mask)
+            torch.cuda.synchronize(comp.device)
+            stages[name] = stages.get(name, 0.0) + (time.perf_counter() - t)
+
+    with torch.cuda.device(comp.device):
+        ws_bytes = int(lib.mt_inflate_spec_workspace(n, chunk))
+        if not ws_bytes:
+            raise ValueError("inflate_stream: %d compressed bytes in chunks of %d; 1 .. 2^31 - 65 bytes and a power of two in "
+                             "64 .. 2^20 are decoded" % (n, chunk))
+        ws = _deflate_alloc(ws_bytes, comp.device)
+        timed(_SPEC_SCAN_STEPS, lambda m: _lib.check(lib.mt_inflate_spec_scan(
+            _ptr(comp), n, chunk, int(unit_limit), span_limit, -1 if n_out is None else int(n_out), m, _ptr(ws), ws_bytes, _stream()),
+            'inflate_spec_scan'))
+
+        def head():
+            h = ws[:32].cpu().numpy()
+            i32 = h.view(np.int32)
+            status = int(i32[0])
+            return {'status': INFLATE_STATUS[status] if 0 <= status < len(INFLATE_STATUS) else status, 'units': int(i32[1]),
+                    'bytes': int(h[8:16].view(np.int64)[0]), 'candidates': int(i32[4]), 'spans': int(i32[5]), 'max_reach': int(i32[6]),
+                    'shortest_unit': int(h[28:32].view(np.uint32)[0])}
+
+        def fail(info):
+            if info['status'] == 'TOO_LONG':
+                err = InflateForeign("inflate_stream: a unit of more than %d bytes or %d compressed bytes: %d candidates in %d bytes"
+                                     % (unit_limit, span_limit, info['candidates'], n))
+            elif info['status'] == 'SIZE':
+                err = IOError("inflate_stream: the stream holds %d bytes, %d were expected" % (info['bytes'], n_out))
+            else:
+                err = IOError("inflate_stream: the DEFLATE stream is damaged (%s)" % info['status'])
+            err.info = info
+            return err
+
+        info = head()
+        if info['status'] != 'OK':
+            raise fail(info)
+        units, spans, total = info['units'], info['spans'], info['bytes']
+        if want_starts:
+            cand, ucand, cap = (int(lib.mt_inflate_spec_workspace_part(n, chunk, k)) for k in range(3))
+            info['positions'] = ws[cand:cand + 8 * info['candidates']].view(torch.int64).clone()
+            info['starts'] = info['positions'][ws[ucand:ucand + 4 * units].view(torch.int32).long()]
+        ws2_bytes = int(lib.mt_inflate_spec_write_workspace(units, spans, total))
+        ws2 = _deflate_alloc(ws2_bytes, comp.device)
+        out = _deflate_alloc(total, comp.device)
+        timed(_SPEC_WRITE_STEPS, lambda m: _lib.check(lib.mt_inflate_spec_write(
+            _ptr(comp), n, chunk, _ptr(ws), ws_bytes, units, spans, _ptr(ws2), ws2_bytes, _ptr(out), total, m, _stream()),
+            'inflate_spec_write'))
+        t2 = time.perf_counter()
+        pieces = max(1, -(-total // INFLATE_CRC_PIECE))
+        crcs = torch.empty(pieces, dtype=torch.int32, device=comp.device)
+        _lib.check(lib.mt_inflate_crc(_ptr(out), total, INFLATE_CRC_PIECE, _ptr(crcs), _stream()), 'inflate_crc')
+        crc = H.crc32_join(crcs.cpu().numpy().view(np.uint32), INFLATE_CRC_PIECE, total - (pieces - 1) * INFLATE_CRC_PIECE)
+        after = head()                                          # a marker that points in front of the stream is found while writing
+        if after['status'] != 'OK':
+            raise fail(dict(info, status=after['status']))
+        if stages is not None:
+            stages['crc'] = stages.get('crc', 0.0) + (time.perf_counter() - t2)
+    return out, crc, info
+
+
 _parse_select_env()
 _select_env = _select

@@ -174,8 +174,10 @@ def read_image_device(fname, device, stages=None):
     DESIGN §6y), CRC-32 and ISIZE of the gzip trailer are checked, the header comes back and is parsed by `_parse_nifti`, and the
     voxels are a view behind it -> (device tensor [z, y, x], spacing, origin, direction).  A stream without restart points or one
     the unit rules refuse (a file of another writer; a damaged one is then refused by zlib), a non-native byte order or a slope /
-    intercept takes the host path: `read_image` and an upload.  A trailer that differs after a successful decode is an IOError.
-    stages['path'] says 'device' or 'host'; the seconds of 'file', 'upload', 'scan', 'write' and 'crc' are added."""
+    intercept takes the host path: `read_image` and an upload — unless the file holds at least ops.INFLATE_SPEC_MIN_OUT bytes and
+    ops.inflate_stream decodes it from block starts it finds in the stream.  A trailer that differs after a successful
+    decode is an IOError.  stages['path'] says 'device' or 'host' and stages['route'] 'restart' or 'speculative'; the seconds of
+    'file', 'upload', 'scan', 'write' (or 'search', 'size', 'chain', 'symbols', 'windows', 'resolve') and 'crc' are added."""
     import time
     import torch
     from .. import ops
@@ -190,12 +192,22 @@ def read_image_device(fname, device, stages=None):
         torch.cuda.synchronize(comp.device)
         stages['file'] = stages.get('file', 0.0) + (t1 - t0)
         stages['upload'] = stages.get('upload', 0.0) + (time.perf_counter() - t1)
+    route = 'restart'
     try:
         out, got, _ = ops.inflate_raw(comp, stages=stages)
     except (ops.InflateForeign, IOError):
-        # no restart points, or a stream the unit rules refuse (BAD / CORRUPT: a valid sync-flushed stream of zlib or pigz is one):
-        # the host reader decides, and zlib refuses a file that is really damaged
+        # no restart points, or a stream the unit rules refuse (BAD / CORRUPT: a valid sync-flushed stream of zlib or pigz is one).  A
+        # file that is large enough (ISIZE, or the compressed size where ISIZE has wrapped at 4 GiB) is decoded from block starts that
+        # are searched in it; otherwise the host reader decides, and zlib refuses a file that is really damaged
         out = None
+        if max(isize, n) >= ops.INFLATE_SPEC_MIN_OUT:
+            try:
+                out, got, found = ops.inflate_stream(comp, stages=stages)
+                route = 'speculative'
+                if stages is not None:
+                    stages['units'] = found['units']
+            except (ops.InflateForeign, IOError):
+                out = None
     if out is not None:
         if got != crc or (int(out.numel()) & 0xffffffff) != isize:
             raise IOError("%s: CRC-32 / size of the decoded bytes (%08x, %d) differ from the gzip trailer (%08x, %d)"
@@ -207,7 +219,7 @@ def read_image_device(fname, device, stages=None):
             if off + count * dt.itemsize > int(out.numel()):
                 raise IOError("%s: the file ends inside its voxels" % fname)
             if stages is not None:
-                stages['path'] = 'device'
+                stages['path'], stages['route'] = 'device', route
             vox = out[off:off + count * dt.itemsize].view(getattr(torch, dt.name)).reshape(shape)
             return vox, tuple(float(i) for i in spacing), tuple(float(i) for i in origin), tuple(float(i) for i in direction)
     if stages is not None:

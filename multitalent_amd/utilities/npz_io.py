@@ -212,8 +212,11 @@ def load_npz_device(fname, key, device, fallback=True, stages=None):
     A stored member, Fortran order, an object dtype or one outside the writer's list, a stream without restart points (a file
     of another writer: ops.InflateForeign) and a stream the unit rules refuse (BAD / CORRUPT / another size: a sync-flushed stream of
     another writer is one; a damaged file is then refused by zlib) are read by `np.load` and uploaded when `fallback` is set, and
-    raise otherwise.  A CRC-32 mismatch after a successful decode is always an IOError.
-    stages['path'] says 'device' or 'host'; the seconds of 'file', 'upload', 'scan', 'write', 'crc' and 'header' are added."""
+    raise otherwise — unless the member holds at least ops.INFLATE_SPEC_MIN_OUT bytes and ops.inflate_stream decodes it from block
+    starts it finds in the stream: a member of numpy's or any other writer's is then read on the device too.  A CRC-32
+    mismatch after a successful decode is always an IOError.
+    stages['path'] says 'device' or 'host' and stages['route'] 'restart' or 'speculative'; the seconds of 'file', 'upload', 'scan',
+    'write' (or 'search', 'size', 'chain', 'symbols', 'windows', 'resolve'), 'crc' and 'header' are added."""
     import time
     import torch
     from .. import ops
@@ -239,16 +242,27 @@ def load_npz_device(fname, key, device, fallback=True, stages=None):
         torch.cuda.synchronize(comp.device)
         stages['file'] = stages.get('file', 0.0) + (t1 - t0)
         stages['upload'] = stages.get('upload', 0.0) + (time.perf_counter() - t1)
+    route = 'restart'
     try:
         out, crc, _ = ops.inflate_raw(comp, n_out=m['usize'], stages=stages)
-    except ops.InflateForeign as e:
-        return host(str(e))
-    except IOError as e:
-        # BAD / CORRUPT / a size mismatch are verdicts of the UNIT rules: a valid stream of another writer that holds empty stored
-        # blocks without a dictionary reset behind them (zlib's Z_SYNC_FLUSH, pigz) fails them too, so zlib decides what is damaged
-        if not fallback:
-            raise
-        return host(str(e))
+    except (ops.InflateForeign, IOError) as e:
+        # InflateForeign: no restart points.  BAD / CORRUPT / a size mismatch are verdicts of the UNIT rules: a valid stream of another
+        # writer that holds empty stored blocks without a dictionary reset behind them (zlib's Z_SYNC_FLUSH, pigz) fails them too.
+        # A member that is large enough is decoded from block starts that are searched in it; what that refuses as
+        # well goes to zlib, which decides what is damaged
+        out = None
+        if m['usize'] >= ops.INFLATE_SPEC_MIN_OUT:
+            try:
+                out, crc, found = ops.inflate_stream(comp, n_out=m['usize'], stages=stages)
+                route = 'speculative'
+                if stages is not None:
+                    stages['units'] = found['units']
+            except (ops.InflateForeign, IOError):
+                out = None
+        if out is None:
+            if isinstance(e, IOError) and not fallback:
+                raise
+            return host(str(e))
     t2 = time.perf_counter()
     if crc != m['crc']:
         raise IOError("%s: CRC-32 of member %s is %08x, its header says %08x" % (fname, key, crc, m['crc']))
@@ -267,7 +281,7 @@ def load_npz_device(fname, key, device, fallback=True, stages=None):
         raise IOError("%s: member %s holds %d bytes, its header describes %d" % (fname, key, m['usize'], hbytes + count * dtype.itemsize))
     t = out[hbytes:].view(getattr(torch, dtype.name)).reshape(shape)
     if stages is not None:
-        stages['path'] = 'device'
+        stages['path'], stages['route'] = 'device', route
         stages['header'] = stages.get('header', 0.0) + (time.perf_counter() - t2)
     return t
 
