@@ -884,7 +884,9 @@ int mt_downsample_seg_nearest(const float* src, int NC, int Di, int Hi, int Wi, 
 
 /* GaussianBlurTransform (data_augmentation_moreDA.py:87-88 -> scipy.ndimage.gaussian_filter per channel): ONE axis pass of the
  * separable filter, dst = correlate1d(src, w) along axis (0 D, 1 H, 2 W) with w[k] ~ exp(-k^2 / 2 sigma^2), radius int(4 sigma + 0.5),
- * 'reflect' boundaries; sigma[NC] per (sample, channel), sigma <= 0 copies that channel.  src != dst. */
+ * 'reflect' boundaries; sigma[NC] per (sample, channel) in DEVICE memory, sigma <= 0 copies that channel.  The radius is never
+ * clamped: the library cannot read a device sigma to refuse it, so a channel whose sigma needs a radius above 32 (sigma >= 8.125)
+ * or is NaN gets NaN in every element of dst.  src != dst. */
 int mt_gaussian_blur_axis(const float* src, float* dst, int NC, int D, int H, int W, int axis, const float* sigma, mt_stream_t stream);
 
 /* NCDHW <-> NDHWC transposes used at the module boundary */

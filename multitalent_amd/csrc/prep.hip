@@ -61,6 +61,8 @@ extern "C" int mt_downsample_seg_nearest(const float* src, int NC, int Di, int H
 //    on any axis yields cval; inside, stencil taps that fall off the array read the MIRRORED coefficient.
 struct PrefilterParams { float* vol; long nlines; int len; long line_stride_outer, line_stride_inner; int inner; long elem_stride; };
 // line index l -> base offset: (l / inner) * line_stride_outer + (l % inner) * line_stride_inner; elements at + k * elem_stride
+#define MT_PF_CHUNK 32           // causal values a thread keeps in registers for the anticausal pass
+#define MT_PF_WARM 40            // inputs in front of a chunk from which its causal values are rebuilt: |z|^40 = 1.3e-23
 __global__ __launch_bounds__(256) void spline_prefilter_kernel(const PrefilterParams P) {
   const double z = -0.26794919243112270647;       // sqrt(3) - 2
   const int n = P.len;
@@ -73,15 +75,38 @@ __global__ __launch_bounds__(256) void spline_prefilter_kernel(const PrefilterPa
     double sum = 6.0 * ((double)p[0] + zn * (double)p[(long)(n - 1) * es]);
     double z1 = z, z2 = zn * zn / z;
     for (int k = 1; k < n - 1; ++k) { sum += 6.0 * (z1 + z2) * (double)p[(long)k * es]; z1 *= z; z2 /= z; }
-    double c = sum / (1.0 - zn * zn);
-    p[0] = (float)c;                                // NB: float storage between the passes, double recursion within a pass
-    double prev = c;
-    // to keep the recursion in double the causal pass is redone from the float inputs: c[k] = 6 s[k] + z c[k-1]
-    for (int k = 1; k < n; ++k) { prev = 6.0 * (double)p[(long)k * es] + z * prev; p[(long)k * es] = (float)prev; }
-    // anticausal: c[n-1] = z/(z^2-1) (z c[n-2] + c[n-1]);  c[k] = z (c[k+1] - c[k])
-    double last = (z / (z * z - 1.0)) * (z * (double)p[(long)(n - 2) * es] + prev);
-    p[(long)(n - 1) * es] = (float)last;
-    for (int k = n - 2; k >= 0; --k) { last = z * (last - (double)p[(long)k * es]); p[(long)k * es] = (float)last; }
+    const double c0 = sum / (1.0 - zn * zn);
+    // Both recursions run in double and the line is rounded to float32 ONCE, when the result is stored (float storage between the
+    // passes over the axes only).  The anticausal pass needs the causal values c+[k] = 6 s[k] + z c+[k-1] from the back, and a line
+    // does not fit in registers, so it goes chunk by chunk from the end: the causal values of a chunk are recomputed from the inputs
+    // in front of it — from c+[0] where the chunk starts within MT_PF_WARM elements of the line's start, else from MT_PF_WARM elements
+    // before it with c+ = 0 there (what that drops is below |z|^40 = 1.3e-23 of the line) — and kept in registers while the
+    // anticausal pass  c[n-1] = z/(z^2-1) (z c+[n-2] + c+[n-1]);  c[k] = z (c[k+1] - c+[k])  overwrites the chunk.  Only elements of
+    // the chunk are written, and every read of an input lies in front of a chunk not yet written.
+    const double g = z / (z * z - 1.0);
+    double next = 0.0;
+    for (int a = ((n - 1) / MT_PF_CHUNK) * MT_PF_CHUNK; a >= 0; a -= MT_PF_CHUNK) {
+      const int len = n - a < MT_PF_CHUNK ? n - a : MT_PF_CHUNK;
+      int j = a - MT_PF_WARM;
+      double prev = 0.0;
+      if (j <= 0) { prev = c0; j = 1; }
+      for (int k = j; k < a; ++k) prev = 6.0 * (double)p[(long)k * es] + z * prev;
+      const double before = prev;                   // c+[a-1] (a > 0)
+      double cp[MT_PF_CHUNK];
+#pragma unroll
+      for (int i = 0; i < MT_PF_CHUNK; ++i) {
+        if (i < len) { prev = (a + i == 0) ? c0 : 6.0 * (double)p[(long)(a + i) * es] + z * prev; }
+        cp[i] = prev;
+      }
+#pragma unroll
+      for (int i = MT_PF_CHUNK - 1; i >= 0; --i) {
+        if (i < len) {
+          if (a + i == n - 1) next = g * (z * (i > 0 ? cp[i > 0 ? i - 1 : 0] : before) + cp[i]);
+          else next = z * (next - cp[i]);
+          p[(long)(a + i) * es] = (float)next;
+        }
+      }
+    }
   }
 }
 extern "C" int mt_spline_prefilter3(float* vol, int NC, int D, int H, int W, int axes, mt_stream_t stream) {
@@ -138,7 +163,9 @@ extern "C" int mt_affine_sample(const float* src, int N, int C, int D, int H, in
 // w[k] = exp(-k^2 / (2 sigma^2)) / sum, k = -r..r, r = int(4 sigma + 0.5) (truncate = 4) and scipy's default 'reflect' boundary
 // (half-sample symmetric: d c b a | a b c d | d c b a).  One launch per axis; sigma per (sample, channel) — sigma <= 0 copies the
 // channel (the transform blurs only some channels of some samples).  HBM-bound: one read (the 2r+1 taps of neighbouring threads
-// overlap in L1/L2) and one write per element and pass.
+// overlap in L1/L2) and one write per element and pass.  The radius is never clamped (a clamped radius is a different filter): sigma
+// lives on the device, so a channel whose sigma needs a radius above MT_BLUR_MAXR (sigma >= 8.125) or is NaN cannot be refused on the
+// host — every element of that channel is written as NaN instead.
 struct BlurParams { const float* src; float* dst; const float* sigma; int NC, D, H, W, axis; };
 #define MT_BLUR_MAXR 32
 __global__ __launch_bounds__(256) void gaussian_blur_axis_kernel(const BlurParams P) {
@@ -149,9 +176,10 @@ __global__ __launch_bounds__(256) void gaussian_blur_axis_kernel(const BlurParam
   const float* src = P.src + (size_t)nc * V;
   float* dst = P.dst + (size_t)nc * V;
   int r = 0;
-  if (sg > 0.f) {
+  // written so that a NaN sigma is refused as well: it fails both comparisons
+  const bool refused = !(sg <= 0.f) && !(4.0 * (double)sg + 0.5 < (double)(MT_BLUR_MAXR + 1));
+  if (sg > 0.f && !refused) {
     r = (int)(4.0 * (double)sg + 0.5);
-    if (r > MT_BLUR_MAXR) r = MT_BLUR_MAXR;
     if (threadIdx.x == 0) {
       double s = 0.0;
       for (int k = -r; k <= r; ++k) s += exp(-0.5 * (double)k * k / ((double)sg * sg));
@@ -163,6 +191,7 @@ __global__ __launch_bounds__(256) void gaussian_blur_axis_kernel(const BlurParam
   const long stride = P.axis == 0 ? (long)P.H * P.W : (P.axis == 1 ? P.W : 1);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < V; i += (long)gridDim.x * 256) {
     if (sg <= 0.f) { dst[i] = src[i]; continue; }
+    if (refused) { dst[i] = __builtin_nanf(""); continue; }
     const int pos = (int)((i / stride) % len);
     const long base = i - (long)pos * stride;
     double acc = 0.0;                                     // scipy's correlate1d accumulates in double

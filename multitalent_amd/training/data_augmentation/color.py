@@ -37,15 +37,29 @@ class GaussianNoiseDevice:
         return data
 
 
+BLUR_MAX_RADIUS = 32          # mt_gaussian_blur_axis never clamps the radius int(4 sigma + 0.5): a larger one gives a NaN channel
+
+
+def check_blur_sigma(sigma, who):
+    """ValueError for a sigma mt_gaussian_blur_axis cannot filter with: a radius above BLUR_MAX_RADIUS (sigma >= 8.125) or a NaN.
+    The comparison is the kernel's, in double on the float32 value; -> the sigmas as a float32 array."""
+    sg = np.asarray(sigma, dtype=np.float32)
+    ok = (sg <= 0) | (4.0 * sg.astype(np.float64) + 0.5 < BLUR_MAX_RADIUS + 1)          # false for a NaN as well
+    if not ok.all():
+        raise ValueError("%s: sigma %s needs a radius above %d (or is NaN); the device filter never clamps a radius"
+                         % (who, sg[~ok], BLUR_MAX_RADIUS))
+    return sg
+
+
 def gaussian_filter_device(x, sigma):
     """scipy.ndimage.gaussian_filter(x[n, c], sigma[n, c], order=0) (mode 'reflect', truncate 4) for every (sample, channel) of a
     [N, C, D, H, W] device tensor; sigma <= 0 leaves that channel untouched.  Axis order D, H, W like scipy; every pass rounds to
-    float32 like scipy does for float32 input."""
+    float32 like scipy does for float32 input.  A sigma whose radius int(4 sigma + 0.5) exceeds 32, or a NaN, is a ValueError."""
     assert x.is_cuda and x.dim() == 5 and x.dtype == torch.float32
+    N, C, D, H, W = (int(i) for i in x.shape)
+    sg = torch.as_tensor(check_blur_sigma(sigma, 'gaussian_filter_device').reshape(N * C)).to(x.device)
     lib = _lib.load()
     st = torch.cuda.current_stream(x.device).cuda_stream
-    N, C, D, H, W = (int(i) for i in x.shape)
-    sg = torch.as_tensor(np.asarray(sigma, dtype=np.float32).reshape(N * C)).to(x.device)
     src = x.contiguous()
     t0, t1 = torch.empty_like(src), torch.empty_like(src)          # D: src -> t0, H: t0 -> t1, W: t1 -> t0 (the input is never written)
     for axis, (a, b) in enumerate(((src, t0), (t0, t1), (t1, t0))):
@@ -60,6 +74,7 @@ class GaussianBlurDevice:
     probability p_per_channel with its own sigma ~ U(blur_sigma)."""
 
     def __init__(self, blur_sigma=(0.5, 1.), different_sigma_per_channel=True, p_per_channel=0.5, p_per_sample=0.2):
+        check_blur_sigma(blur_sigma, 'GaussianBlurDevice(blur_sigma)')
         self.sigma, self.per_channel, self.ppc, self.p = blur_sigma, different_sigma_per_channel, p_per_channel, p_per_sample
 
     def _draw(self):

@@ -14,8 +14,22 @@ import torch
 from ... import _lib
 
 
-def _sampler_source(x, mats, order, is_seg, planar):
+def _check_seg_cval(cval):
+    """The per-label rule (mt_affine_sample mode 11) writes 0 for a coordinate outside the volume.  batchgenerators'
+    interpolate_img interpolates every label's indicator with the same cval and assigns the label where the result is >= 0.5, in
+    ascending order: with cval >= 0.5 every label's indicator qualifies outside the volume, so the reference writes the volume's
+    LARGEST label there.  That is not on the device path (nnU-Net passes -1); it is refused, never silently different."""
+    if float(cval) >= 0.5:
+        raise NotImplementedError("segmentation sampling (order 1, per-label rule) with cval = %g >= 0.5: batchgenerators' "
+                                  "interpolate_img would assign the largest label of the volume to every coordinate outside it "
+                                  "(each label's indicator interpolates to cval >= 0.5 there); the device kernel writes 0. "
+                                  "Use a cval below 0.5 (nnU-Net: -1)" % float(cval))
+
+
+def _sampler_source(x, mats, order, is_seg, planar, cval=0.0):
     """the (source, mode, mats) of one sampling call: order 3 samples the prefiltered B-spline coefficients."""
+    if is_seg and order == 1:
+        _check_seg_cval(cval)
     assert x.is_cuda and x.dim() == 5 and x.dtype == torch.float32
     lib = _lib.load()
     st = torch.cuda.current_stream(x.device).cuda_stream
@@ -37,8 +51,9 @@ def _sampler_source(x, mats, order, is_seg, planar):
 
 def affine_sample(x, mats, out_shape, order, cval=0.0, is_seg=False, planar=False):
     """x: [N, C, D, H, W] float32 device tensor; mats: [N, 12] (row-major 3x3 M then the centre) so that output voxel o reads
-    input coordinate M (o - (O-1)/2) + centre; order 0 / 1 / 3; is_seg with order 1 = batchgenerators' per-label rule."""
-    src, mode, mats = _sampler_source(x, mats, order, is_seg, planar)
+    input coordinate M (o - (O-1)/2) + centre; order 0 / 1 / 3; is_seg with order 1 = batchgenerators' per-label rule, which
+    the kernel implements for cval < 0.5 only (`_check_seg_cval`: NotImplementedError otherwise)."""
+    src, mode, mats = _sampler_source(x, mats, order, is_seg, planar, cval)
     N, C, D, H, W = (int(i) for i in x.shape)
     st = torch.cuda.current_stream(x.device).cuda_stream
     out = torch.empty((N, C) + tuple(int(i) for i in out_shape), dtype=torch.float32, device=x.device)
@@ -51,7 +66,7 @@ def warp_sample(x, mats, out_shape, order, field, alpha, cval=0.0, is_seg=False,
     """affine_sample over the displaced mesh: output voxel o reads M (o - (O-1)/2 + alpha[n] field[n, :, o]) + centre.
     field: [N, 3, OD, OH, OW] float32 device tensor (planar: [N, 2, OH, OW], one field for all slices); alpha: [N].  A sample
     with alpha 0 never reads its field."""
-    src, mode, mats = _sampler_source(x, mats, order, is_seg, planar)
+    src, mode, mats = _sampler_source(x, mats, order, is_seg, planar, cval)
     N, C, D, H, W = (int(i) for i in x.shape)
     out_shape = tuple(int(i) for i in out_shape)
     assert field.is_cuda and field.dtype == torch.float32 and field.is_contiguous()
@@ -131,6 +146,8 @@ class SpatialTransformDevice:
         self.last_elastic = self.last_mats = None
         if border_mode_data != 'constant' or border_mode_seg != 'constant':
             raise NotImplementedError("only constant borders (nnU-Net's setting) are on the device path")
+        if order_seg == 1:
+            _check_seg_cval(border_cval_seg)
         self.patch_size = tuple(int(i) for i in patch_size)
         self.dist = patch_center_dist_from_border
         self.do_rotation, self.angles = do_rotation, (angle_x, angle_y, angle_z)
