@@ -681,8 +681,10 @@ int mt_crop_nonzero(const float* data, int C, int D, int H, int W, const uint8_t
  *   NaN for mean and sd.  At most 16 channels.  ws: mt_masked_moments_workspace(C, V) bytes of device scratch, 8-byte aligned.
  * mt_intensity_normalize: in place on one channel x[V]:  x = clip(x, lo, hi) when clip != 0, then x = (x - m) / (s + eps) in float32
  *   with a true division (numpy's arithmetic order), where (m, s) = (mean, sd), or (float)stats[1], (float)stats[2] of a device
- *   triple that mt_masked_moments wrote when stats != NULL.  seg != NULL: voxels where seg[v] >= 0 does not hold become 0 (both masked
- *   forms of the reference, `data[seg < 0] = 0` after normalising and `data[mask] = ...; data[mask == 0] = 0`, give this result).
+ *   triple that mt_masked_moments wrote when stats != NULL.  The clip is np.clip's two comparisons: a NaN voxel passes it and stays
+ *   NaN.  seg != NULL: voxels with seg[v] < 0 become 0, the reference's `data[seg < 0] = 0` after normalising; its other masked form,
+ *   `mask = seg >= 0; data[mask] = ...; data[mask == 0] = 0`, gives the same result for every seg but a NaN one, which `seg < 0`
+ *   leaves normalised and `mask == 0` would zero (a label map holds no NaN; the kernel follows `seg < 0`).
  * mt_label_counts / mt_label_locations: the class locations of _run_internal (:340-351).  seg: float32 label map [V]; a voxel belongs
  *   to slot table[(int)seg[v]] when seg[v] is an integer in 0..L-1 and that entry is < nslots (table: L device bytes, 255 = no slot;
  *   nslots <= 255).  mt_label_counts: counts[slot] (device int64) = number of voxels of the slot; it also leaves, in ws, the

@@ -133,8 +133,11 @@ extern "C" int mt_masked_moments(const float* data, int C, long V, int pred, con
 struct NormParams { float* x; const float* seg; long V; int clip, masked; float lo, hi, mean, sd, eps; const double* stats; };
 
 __device__ __forceinline__ float pp_norm1(float x, float s, const NormParams& P, float mean, float den) {
-  if (P.masked && !(s >= 0.f)) return 0.f;
-  if (P.clip) x = fminf(fmaxf(x, P.lo), P.hi);
+  if (P.masked && s < 0.f) return 0.f;      // numpy's data[seg < 0] = 0: a NaN in seg zeroes nothing
+  if (P.clip) {                             // np.clip as two comparisons: a NaN voxel fails both and passes unchanged
+    x = x < P.lo ? P.lo : x;
+    x = x > P.hi ? P.hi : x;
+  }
   return (x - mean) / den;                 // a true float32 division, as numpy's (x - m) / s: no reciprocal
 }
 
@@ -225,7 +228,11 @@ __global__ __launch_bounds__(PP_THREADS) void label_units_kernel(const LabelPara
             }
           }
           const int32_t next = cur + (int32_t)__popcll(m);
-          if (lane == owner) { if (hi == 0) c[0] = next; else if (hi == 1) c[1] = next; else if (hi == 2) c[2] = next; else c[3] = next; }
+          // four selects, no branches: the if / else chain on the uniform `hi` was compiled (ROCm 7 hipcc, -O3) so that hi == 3
+          // stored into c[0] and left c[3] alone, and slots 192..254 were never counted (tests/test_datapath_kernels_gpu.py)
+          const bool own = lane == owner;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) c[k] = (own && hi == k) ? next : c[k];
           todo &= ~m;
         }
       }
