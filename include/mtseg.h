@@ -495,8 +495,9 @@ int mt_resample_classify(const float* probs, int C, int D, int H, int W, int OD,
  * Arithmetic = numpy's float16 mean, bit for bit: float32 accumulation in member order ((m0 + m1) + m2) + ..., ONE IEEE float32
  * division by (float)K, ONE round-to-nearest-even to float16, float16 subnormals kept.  The label is decided on that ROUNDED
  * float16 mean: argmax with the first maximum winning, or (use_regions) the last channel i with mean_i > 0.5 gives
- * class_order[i] (DEVICE int32[C], as in mt_resample_classify), else 0.  NaN members are outside the contract (the label of such
- * a voxel is unspecified; the stored mean is still numpy's).
+ * class_order[i] (DEVICE int32[C], as in mt_resample_classify), else 0; the label is a uint8, so a class_order entry above 255
+ * is stored as its low byte (entry & 255), the same on every store path.  A NaN mean follows numpy: np.argmax picks the first NaN
+ * channel of a voxel, and a NaN mean is never > 0.5; the stored mean is numpy's.
  * out: uint8 [FD][FH][FW]; the box is written at offset (bD, bH, bW), which must lie inside the volume, clipped to the volume;
  * voxels outside the box are not touched.  mean: NULL, or float16 [C][mean_stride], mean_stride >= V (only the V voxels of each
  * channel are written).  Where the member pointers, mean, chan_stride and mean_stride are multiples of 8 elements every lane
@@ -721,7 +722,9 @@ int mt_label_locations(const float* seg, int D, int H, int W, const uint8_t* tab
  *   variance = (sum(d*d) - sum(d)^2/V)/V.  The shift is a sample of the channel, so (shift - mean)^2 <= V * variance and the
  *   subtraction loses at most log2(V) <= 31 of the 53 bits: a channel whose mean is 100 times (or 10^6 times) its sd keeps its sd.
  *   Per-workgroup partials are combined in a fixed order by a second small launch, no floating-point atomics: bit-identical from
- *   run to run.  A constant channel gives sd 0 exactly.  NaN elements are outside the contract.
+ *   run to run.  A constant channel gives sd 0 exactly.  Non-finite elements follow numpy: a channel that holds a NaN has NaN for
+ *   all four statistics; one that holds an infinity (and no NaN) has its exact min and max, numpy's mean (+-inf, NaN with both signs)
+ *   and a NaN sd.  (The shift is 0 when x[c][0] is not finite.)
  *   ws: mt_channel_stats_workspace(NC, V) bytes of device scratch, 8-byte aligned; a smaller one is MT_EINVAL before any launch.
  * mt_intensity_apply: in place, one launch per 64 channels.  records: HOST array of NC mt_intensity_op_t, one per channel:
  *   MT_INTENSITY_NONE      the channel is neither read nor written;

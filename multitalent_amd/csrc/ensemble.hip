@@ -21,7 +21,8 @@ typedef _Float16 mt_h8 __attribute__((ext_vector_type(8)));
 
 // numpy's np.mean of float16 members: float32 sum in member order, one IEEE division, one RNE rounding to float16 (subnormals
 // kept: the f16 denormal mode of the code object is on, and float32 denormals are not flushed either).  The label is decided on
-// the rounded value widened back.
+// the rounded value widened back.  A NaN mean follows numpy: the argmax takes the first NaN channel, `> 0.5` never holds for it.
+// A class_order entry above 255 is stored as its low byte on every store path (the packed `& 255`, the bytewise cast).
 template <bool WIDE> __global__ __launch_bounds__(256) void ensemble_classify_kernel(const EnsembleParams P) {
   const long groups = (P.V + MT_ENS_VOX - 1) / MT_ENS_VOX;
   const float fk = (float)P.K;
@@ -74,7 +75,7 @@ template <bool WIDE> __global__ __launch_bounds__(256) void ensemble_classify_ke
 #pragma unroll
         for (int j = 0; j < MT_ENS_VOX; ++j) {
           const float m = (float)h[j];
-          if (c == 0 || m > best[j]) { best[j] = m; lab[j] = c; }
+          if (c == 0 || m > best[j] || (m != m && best[j] == best[j])) { best[j] = m; lab[j] = c; }     // np.argmax: the first NaN wins
         }
       }
     }

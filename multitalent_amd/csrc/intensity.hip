@@ -24,16 +24,21 @@ static int ia_stat_blocks(long V) { return mt_stream_blocks((V + 3) / 4, IA_THRE
 // One pass, shifted: with K = x[0] of the channel, every thread accumulates sum(d) and sum(d * d) of d = x - K in double.  K is a
 // sample of the channel, so (K - mean)^2 <= V * variance: the cancellation in  s2 - s1^2 / V  costs at most log2(V) <= 31 of the 53
 // bits, whatever the ratio of mean to sd (a channel of mean 100 and sd 1 has d of order 1).  Min and max are exact in float32.
+// Non-finite elements follow numpy.  The shift is 0 when x[0] is not finite, so d is NaN exactly where x is: sum(d * d) - a sum of
+// non-negative terms, infinite ones included - is NaN exactly when the channel holds a NaN, and then all four statistics are NaN
+// (fminf / fmaxf alone would drop it).  The streaming loop pays nothing for this.  With an infinite element and no NaN, min and
+// max are exact, the mean is numpy's (+-inf, or NaN with both signs) and the sd is NaN.
 struct StatParams { const float* x; long V; int c0, nblk; uint64_t active; double* part; /* [NC][nblk][4]: min, max, s1, s2 */ };
+__device__ __forceinline__ float ia_shift(float x0) { return fabsf(x0) < __builtin_huge_valf() ? x0 : 0.f; }
 
 __global__ __launch_bounds__(IA_THREADS) void channel_stats_kernel(const StatParams P) {
   if (!(P.active >> blockIdx.y & 1ull)) return;
   const int c = P.c0 + (int)blockIdx.y;
   const float* x = P.x + (size_t)c * P.V;
-  const float k = x[0];
+  const float x0 = x[0], k = ia_shift(x0);
   const long nquad = P.V / 4;
   const long gtid = (long)blockIdx.x * IA_THREADS + threadIdx.x, gstride = (long)gridDim.x * IA_THREADS;
-  float lo = k, hi = k;
+  float lo = x0, hi = x0;
   double a1[4] = {0.0, 0.0, 0.0, 0.0}, a2[4] = {0.0, 0.0, 0.0, 0.0};      // one pair of sums per quad component: four short chains
 #pragma unroll 4                 // = IA_STAT_QUADS: the loads of a thread's quads are issued together
   for (long q = gtid; q < nquad; q += gstride) {
@@ -74,8 +79,8 @@ __global__ __launch_bounds__(MT_WAVE) void channel_stats_finalize_kernel(const S
   if (!(P.active >> blockIdx.x & 1ull)) return;
   const int c = P.c0 + (int)blockIdx.x;
   const double* p = P.part + (size_t)c * P.nblk * 4;
-  const double k = (double)P.x[(size_t)c * P.V];
-  double lo = k, hi = k, s1 = 0.0, s2 = 0.0;
+  const double k = (double)ia_shift(P.x[(size_t)c * P.V]);
+  double lo = __builtin_huge_val(), hi = -__builtin_huge_val(), s1 = 0.0, s2 = 0.0;
   for (int b = threadIdx.x; b < P.nblk; b += MT_WAVE) { lo = fmin(lo, p[4 * b]); hi = fmax(hi, p[4 * b + 1]); s1 += p[4 * b + 2]; s2 += p[4 * b + 3]; }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) { lo = fmin(lo, __shfl_xor(lo, off, MT_WAVE)); hi = fmax(hi, __shfl_xor(hi, off, MT_WAVE)); }
@@ -84,7 +89,8 @@ __global__ __launch_bounds__(MT_WAVE) void channel_stats_finalize_kernel(const S
   if (threadIdx.x == 0) {
     const double n = (double)P.V, var = (s2 - s1 * s1 / n) / n;
     double* o = stats + (size_t)c * 4;
-    o[0] = lo; o[1] = hi; o[2] = k + s1 / n; o[3] = var > 0.0 ? sqrt(var) : 0.0;
+    if (s2 != s2) lo = hi = s2;                                   // a NaN element
+    o[0] = lo; o[1] = hi; o[2] = k + s1 / n; o[3] = var > 0.0 ? sqrt(var) : (var != var ? var : 0.0);
   }
 }
 
