@@ -478,6 +478,32 @@ int mt_warp_sample(const float* src, int N, int C, int D, int H, int W, float* d
                    const float* mats /* N x 12, as mt_affine_sample */,
                    const float* field /* [N, 3, OD, OH, OW]; planar: [N, 2, OH, OW] */,
                    const float* alpha /* [N] */, int mode /* 0, 1, 3, 11 */, float cval, int planar, mt_stream_t stream);
+/* The resize unit (resize.hip, resize_line.h): resample_data_or_seg (preprocessing/preprocessing.py:109-197) at every order the
+ * reference's preprocessors use.  skimage.transform.resize(order, mode='edge', anti_aliasing=False) is
+ * scipy.ndimage.zoom(order, mode='nearest', grid_mode=True), the z pass is scipy.ndimage.map_coordinates(order_z, mode='nearest'):
+ * output index o of an axis resized from `in` to `out` samples x = (o + 0.5) * in / out - 0.5 of the line extended by its edge values.
+ * Volumes are [NC, D, H, W] float32; more than INT32_MAX input or output elements, a non-positive extent, a null pointer or an
+ * order other than 0, 1, 3 is MT_EINVAL before any launch.
+ * mt_resize_prefilter3: cubic B-spline prefilter (pole sqrt(3) - 2, gain 6) along the axes of the mask, src -> dst, src == dst
+ *   allowed.  The edge rule needs no padded copy: c+[-1] = 6 x[0] / (1 - z) and
+ *   c[n-1] = -(s z / (1 - z) + (c+[n-1] - s) z / (1 - z^2)), s = 6 x[n-1] / (1 - z).  Double recursion, one rounding to float32 per
+ *   pass; a line of length 1 is copied.  With src != dst an axis that is not filtered is still copied by the first pass.
+ * mt_resize: dst[NC, OD, OH, OW] with one order per axis.  An axis with in == out is copied whatever its order and must NOT be
+ *   prefiltered; every other axis of order 3 must be.  Order 0: floor(x + 0.5) clamped; order 1: x clamped to [0, n - 1]; order 3: x
+ *   is not clamped, taps floor(x) - 1 .. floor(x) + 2, and a tap at -2 .. -1 or n .. n + 1 is the coefficient of the extended line,
+ *   c[-m] = x0 + (c[0] - x0) z^m with x0 = ((4 + z) c[0] + c[1]) / (5 + z) (mirrored at the end; n == 1: the value), folded into the
+ *   weights of the two stored coefficients next to the edge.  Coordinates, weights and accumulation in double, output float32.
+ *   A 3D resize gives one order on all axes; a per-slice resize leaves the anisotropic axis (any of the three) at in == out; the z pass
+ *   changes one axis.  src != dst.
+ * mt_resize_labels: batchgenerators' resize_segmentation(order 1) on the axes that change: the largest label whose order-1
+ *   interpolated indicator is >= 0.5 (labels apply in ascending order), 0 where none is; -1 is a label like any other.
+ * mt_resize_labels_axis: the z pass of a label map (preprocessing.py:176-184) along `axis` (0 D, 1 H, 2 W) to out_n: the same rule
+ *   with the weight STRICTLY above 0.5 (np.round sends 0.5 to 0). */
+int mt_resize_prefilter3(const float* src, float* dst, int NC, int D, int H, int W, int axes /* bit 0 W, 1 H, 2 D */, mt_stream_t stream);
+int mt_resize(const float* src, int NC, int D, int H, int W, float* dst, int OD, int OH, int OW, int order_d, int order_h, int order_w,
+              mt_stream_t stream);
+int mt_resize_labels(const float* src, int NC, int D, int H, int W, float* dst, int OD, int OH, int OW, mt_stream_t stream);
+int mt_resize_labels_axis(const float* src, int NC, int D, int H, int W, int axis, int out_n, float* dst, mt_stream_t stream);
 /* Export post-processing: save_segmentation_nifti_from_softmax (segmentation_export.py:27-160) without the
  * resampled 47-channel intermediate — probabilities [C, D, H, W] are interpolated at the OD x OH x OW grid of the original
  * spacing (order 1, skimage/scipy half-pixel rule, edge clamp; sep_axis in 0..2 = the anisotropic axis sampled nearest as in

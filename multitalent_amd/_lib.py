@@ -148,6 +148,10 @@ SIGNATURES = {
     'mt_affine_sample': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _f, _i, _vp]),
     'mt_gaussian_blur_axis_zero': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _P(_f), _vp]),
     'mt_warp_sample': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _i, _vp]),
+    'mt_resize_prefilter3': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'mt_resize': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mt_resize_labels': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
+    'mt_resize_labels_axis': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'mt_resample_classify': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _l, _l, _l, _i, _i, _i, _vp]),
     'mt_ensemble_classify': (_i, [_P(_vp), _i, _i, _i, _i, _i, _l, _vp, _i, _vp, _l, _l, _l, _i, _i, _i, _vp, _l, _vp]),
     'mt_deflate_workspace': (_sz, [_l, _i]),

@@ -751,6 +751,74 @@ def downsample_seg_nearest(seg, out_spatial, remove_minus_one=False, out=None):
     return out
 
 
+# ---- the resize unit (csrc/resize.hip): volumes are [NC, D, H, W] float32, contiguous ------------------------------------------------
+_RESIZE = "the resize unit runs"
+RESIZE_ORDERS = (0, 1, 3)
+RESIZE_MAX_ELEMENTS = 2 ** 31 - 1
+
+
+def _resize_volume(x, who):
+    if not torch.is_tensor(x) or x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("%s: a contiguous float32 [NC, D, H, W] tensor is expected" % who)
+    _require_device(_RESIZE, x)
+    return tuple(int(i) for i in x.shape)
+
+
+def _resize_out(x, out, shape, who):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("%s: out must be a contiguous float32 tensor of shape %s on the input's device" % (who, tuple(shape)))
+    return out
+
+
+def resize_prefilter3(x, axes, out=None):
+    """mt_resize_prefilter3: cubic B-spline coefficients of x [NC, D, H, W] along the axes of the mask (bit 0 W, bit 1 H, bit 2 D) for
+    lines extended by their edge values (scipy's 'nearest').  out: None (a new tensor), x itself (in place) or another tensor."""
+    NC, D, H, W = _resize_volume(x, "resize_prefilter3")
+    out = _resize_out(x, out, (NC, D, H, W), "resize_prefilter3")
+    _lib.check(_lib.load().mt_resize_prefilter3(_ptr(x), _ptr(out), NC, D, H, W, int(axes), _stream()), 'resize_prefilter3')
+    return out
+
+
+def resize(x, out_shape, orders, out=None):
+    """mt_resize: x [NC, D, H, W] -> [NC, *out_shape] with one order (0, 1, 3) per axis; an axis of order 3 that changes must hold
+    prefilter coefficients (resize_prefilter3), an axis that keeps its extent is copied and must not."""
+    NC, D, H, W = _resize_volume(x, "resize")
+    out_shape = tuple(int(i) for i in out_shape)
+    orders = tuple(int(i) for i in orders)
+    if len(out_shape) != 3 or len(orders) != 3:
+        raise ValueError("resize: three output extents and three orders are expected, got %s and %s" % (out_shape, orders))
+    out = _resize_out(x, out, (NC,) + out_shape, "resize")
+    if out.data_ptr() == x.data_ptr():
+        raise ValueError("resize: out must not be the input")
+    _lib.check(_lib.load().mt_resize(_ptr(x), NC, D, H, W, _ptr(out), *out_shape, *orders, _stream()), 'resize')
+    return out
+
+
+def resize_labels(seg, out_shape, out=None):
+    """mt_resize_labels: resize_segmentation(order 1) of label maps [NC, D, H, W] on the axes that change."""
+    NC, D, H, W = _resize_volume(seg, "resize_labels")
+    out_shape = tuple(int(i) for i in out_shape)
+    if len(out_shape) != 3:
+        raise ValueError("resize_labels: three output extents are expected, got %s" % (out_shape,))
+    out = _resize_out(seg, out, (NC,) + out_shape, "resize_labels")
+    _lib.check(_lib.load().mt_resize_labels(_ptr(seg), NC, D, H, W, _ptr(out), *out_shape, _stream()), 'resize_labels')
+    return out
+
+
+def resize_labels_axis(seg, axis, out_n, out=None):
+    """mt_resize_labels_axis: the z pass of label maps [NC, D, H, W] along `axis` (0 D, 1 H, 2 W) to `out_n` elements."""
+    NC, D, H, W = _resize_volume(seg, "resize_labels_axis")
+    shape = [D, H, W]
+    if int(axis) not in (0, 1, 2):
+        raise ValueError("resize_labels_axis: axis is 0, 1 or 2, got %r" % (axis,))
+    shape[int(axis)] = int(out_n)
+    out = _resize_out(seg, out, (NC,) + tuple(shape), "resize_labels_axis")
+    _lib.check(_lib.load().mt_resize_labels_axis(_ptr(seg), NC, D, H, W, int(axis), int(out_n), _ptr(out), _stream()), 'resize_labels_axis')
+    return out
+
+
 # ---- the data path: post-processing, cropping, training-case preprocessing, evaluation, dataset analysis -----------------------------
 MAX_VOXELS = 2 ** 31 - 1         # int32 linear indices and ranks in every kernel of the data path
 CC_MAX_VOXELS = CROP_MAX_VOXELS = LABEL_MAX_VOXELS = FG_MAX_VOXELS = MAX_VOXELS

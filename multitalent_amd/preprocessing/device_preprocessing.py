@@ -11,6 +11,11 @@ Labels (order 1, separate z with order 0): batchgenerators' resize_segmentation 
 ascending labels overwrite where it reaches 0.5 — is `mt_affine_sample` mode 11 on a volume edge-padded by one voxel.
 Normalisation: `mt_masked_moments` (per-case mean / sd in double) and `mt_intensity_normalize` (one fused in-place pass).
 Class locations: `mt_label_counts` / `mt_label_locations`; the host draws the reference's random ranks, the device resolves them.
+Other orders (`resample_data_or_seg`, `resample_patient`: data at order 0, 1, 3 with order_z 0, 1, 3; labels at order 0, 1 with order_z
+0, 1 — what GenericPreprocessor_linearResampling and Preprocessor3DDifferentResampling ask for) run on the resize unit, csrc/resize.hip:
+`mt_resize_prefilter3` (scipy's 'nearest' edge rule in closed form, no padded copy), `mt_resize` (one order per axis, the
+anisotropic axis addressed by its stride), `mt_resize_labels`, `mt_resize_labels_axis`.  `resample_data` / `resample_seg` above keep
+their launches.
 The crop to the non-zero region in front of this is `device_cropping.py` (also on the device); file I/O stays with the caller."""
 import numpy as np
 import torch
@@ -74,6 +79,75 @@ def resampling_plan(shape, original_spacing, target_spacing, force_separate_z=No
     if axis is not None and len(axis) != 1:
         sep = False
     return new_shape, sep, axis
+
+
+def _resize_stage(x, out_shape, order, is_seg):
+    """One resize_fn call of the reference over the axes of x [C, X, Y, Z] (float32, contiguous) that change: skimage's resize at
+    `order` for data and for labels at order 0, batchgenerators' resize_segmentation for labels at order 1."""
+    if tuple(x.shape[1:]) == tuple(out_shape):
+        return x
+    if is_seg and order == 1:
+        return ops.resize_labels(x, out_shape)
+    axes = sum(1 << (2 - a) for a in range(3) if order == 3 and x.shape[1 + a] != out_shape[a])        # mask: bit 0 is the last axis
+    return ops.resize(ops.resize_prefilter3(x, axes) if axes else x, out_shape, (order,) * 3)
+
+
+def resample_data_or_seg(data, new_shape, is_seg, axis=None, order=3, do_separate_z=False, order_z=0):
+    """The reference's resample_data_or_seg (preprocessing.py:109-197) for a [C, X, Y, Z] device tensor, on the resize unit
+    (csrc/resize.hip).  Data: order 0, 1 or 3 with order_z 0, 1 or 3 (skimage's resize as scipy.ndimage.zoom(mode='nearest',
+    grid_mode=True), the z pass as map_coordinates(mode='nearest')).  Labels: order 0 or 1 (resize_segmentation) with order_z 0 or 1
+    (per label, strictly above one half); a label order of 3 is not on this path.  With do_separate_z every slice across `axis` is
+    resized on its own, whichever of the three axes that is (addressed by strides, nothing is permuted), then the axis is resampled
+    with order_z; the intermediate is float32, which for float32 input is the reference's own rounding.  The result has the dtype
+    of the input; an input that already has `new_shape` is returned as it is."""
+    if not torch.is_tensor(data) or not data.is_cuda:
+        raise RuntimeError("multitalent_amd: device pre-processing runs on a HIP device only; there is no CPU fallback")
+    assert data.dim() == 4, "data must be (c, x, y, z)"
+    assert len(new_shape) == data.dim() - 1
+    order, order_z = int(order), int(order_z)
+    if is_seg:
+        if order not in (0, 1) or order_z not in (0, 1):
+            raise NotImplementedError("label maps are resampled with order 0 or 1 (order_z 0 or 1) on this path, got order %d / order_z %d"
+                                      % (order, order_z))
+    elif order not in ops.RESIZE_ORDERS or order_z not in ops.RESIZE_ORDERS:
+        raise NotImplementedError("data is resampled with order 0, 1 or 3 on this path, got order %d / order_z %d" % (order, order_z))
+    shape = tuple(int(i) for i in data.shape[1:])
+    new_shape = tuple(int(i) for i in new_shape)
+    if shape == new_shape:
+        return data
+    x = data.float().contiguous()
+    if do_separate_z:
+        assert len(axis) == 1, "only one anisotropic axis supported"
+        ax = int(axis[0])
+        mid = tuple(shape[a] if a == ax else new_shape[a] for a in range(3))
+        out = _resize_stage(x, mid, order, is_seg)
+        if shape[ax] != new_shape[ax]:
+            if is_seg and order_z != 0:
+                out = ops.resize_labels_axis(out, ax, new_shape[ax])
+            else:
+                if order_z == 3:
+                    out = ops.resize_prefilter3(out, 1 << (2 - ax), out=None if out is x else out)
+                out = ops.resize(out, new_shape, tuple(order_z if a == ax else 0 for a in range(3)))
+    else:
+        out = _resize_stage(x, new_shape, order, is_seg)
+    return out.to(data.dtype)
+
+
+def resample_patient(data, seg, original_spacing, target_spacing, order_data=3, order_seg=0, force_separate_z=False,
+                     order_z_data=0, order_z_seg=0, separate_z_anisotropy_threshold=3):
+    """The reference's resample_patient (preprocessing.py:38-106) for device tensors [C, X, Y, Z] (either may be None):
+    -> (data, seg) at round(original_spacing / target_spacing * shape).  force_separate_z: None decides by the anisotropy of the
+    spacings, True / False forces it."""
+    assert not ((data is None) and (seg is None))
+    if data is not None:
+        assert data.dim() == 4, "data must be c x y z"
+    if seg is not None:
+        assert seg.dim() == 4, "seg must be c x y z"
+    shape = (data if data is not None else seg).shape[1:]
+    new_shape, sep, axis = resampling_plan(shape, original_spacing, target_spacing, force_separate_z, separate_z_anisotropy_threshold)
+    data_reshaped = resample_data_or_seg(data, new_shape, False, axis, order_data, sep, order_z=order_z_data) if data is not None else None
+    seg_reshaped = resample_data_or_seg(seg, new_shape, True, axis, order_seg, sep, order_z=order_z_seg) if seg is not None else None
+    return data_reshaped, seg_reshaped
 
 
 def _to_device(x):

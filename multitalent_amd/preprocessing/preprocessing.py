@@ -4,7 +4,10 @@ the files on the host, then crop to the non-zero region (`device_cropping`: `mt_
 `mt_affine_sample`).  Training cases (`run` / `_run_internal` / `preprocess_training_case`): the cropped case is resampled with its
 label map (order 1 per label, `mt_affine_sample` mode 11), normalised with any of the schemes "CT", "CT2", "noNorm" and the
 per-case z-score, each with or without `use_mask_for_norm` (`mt_masked_moments`, `mt_intensity_normalize`), and its class locations
-are sampled (`mt_label_counts`, `mt_label_locations`); the host reads and writes the files.  There is no CPU fallback."""
+are sampled (`mt_label_counts`, `mt_label_locations`); the host reads and writes the files.  There is no CPU fallback.
+`GenericPreprocessor_linearResampling` (preprocessing.py:402-407) and `Preprocessor3DDifferentResampling` (:410-491) differ in the
+resampling orders alone and take them to the resize unit (`device_preprocessing.resample_data_or_seg`); `PREPROCESSORS` names the
+classes a plans file may ask for."""
 import os
 import pickle
 from concurrent.futures import ThreadPoolExecutor
@@ -90,11 +93,10 @@ class GenericPreprocessor(object):
         data = torch.nan_to_num(data, nan=0.0, posinf=None, neginf=None) if torch.isnan(data).any() else data
         new_shape, sep, axis = dp.resampling_plan(data.shape[1:], spacing, target_spacing, force_separate_z,
                                                   self.resample_separate_z_anisotropy_threshold)
-        out = dp.resample_data(data, new_shape, axis, sep)
+        seg_in = dp._to_device(seg).float() if seg is not None else None
+        out, seg = self._resample(data, seg_in, new_shape, axis, sep)
         out = out.clone() if out is data else out.contiguous()
         if seg is not None:
-            seg_in = dp._to_device(seg).float()
-            seg = dp.resample_seg(seg_in, new_shape, axis, sep)
             seg = seg.clone() if seg is seg_in else seg
             seg[seg < -1] = 0
         properties["size_after_resampling"] = tuple(int(i) for i in out.shape[1:])
@@ -103,6 +105,11 @@ class GenericPreprocessor(object):
         if not return_device:
             out, seg = out.cpu().numpy(), (seg.cpu().numpy() if seg is not None else None)
         return out, seg, properties
+
+    def _resample(self, data, seg, new_shape, axis, sep):
+        """The resampling of the full path: float32 device tensors [C, X, Y, Z] (seg may be None) -> the same at `new_shape`.  Here
+        order 3 / z 0 for the data and order 1 / z 0 for the labels, on `mt_spline_prefilter3` + `mt_affine_sample`."""
+        return dp.resample_data(data, new_shape, axis, sep), (dp.resample_seg(seg, new_shape, axis, sep) if seg is not None else None)
 
     def preprocess_test_case(self, data_files, target_spacing, seg_file=None, force_separate_z=None, return_device=False):
         """preprocessing.py:313-321.  The uncropped float32 volume is uploaded once and cropped on the device; a volume beyond the
@@ -200,3 +207,44 @@ class GenericPreprocessor(object):
                         pending.pop(0).result()
                 for p in pending:
                     p.result()
+
+
+class _ResizeUnitPreprocessor(GenericPreprocessor):
+    """A preprocessor whose resampling orders differ from the default's: every case takes the full path of the reference's
+    `resample_and_normalize` (the label map or non-zero mask is resampled by the label rule, every scheme is available), and the
+    resampling is `device_preprocessing.resample_data_or_seg` on the resize unit (`mt_resize_prefilter3`, `mt_resize`,
+    `mt_resize_labels`, `mt_resize_labels_axis`) with the orders of the class."""
+    resample_order_z_data = 0
+    resample_order_z_seg = 0
+
+    def resample_and_normalize(self, data, target_spacing, properties, seg=None, force_separate_z=None, return_device=False,
+                               keep_seg=False):
+        schemes = [self.normalization_scheme_per_modality[c] for c in range(len(data))]
+        use_mask = [bool(self.use_nonzero_mask[c]) for c in range(len(data))]
+        return self._resample_and_normalize_full(data, target_spacing, properties, seg, force_separate_z, return_device, schemes,
+                                                 use_mask)
+
+    def _resample(self, data, seg, new_shape, axis, sep):
+        out = dp.resample_data_or_seg(data, new_shape, False, axis, self.resample_order_data, sep, self.resample_order_z_data)
+        if seg is not None:
+            seg = dp.resample_data_or_seg(seg, new_shape, True, axis, self.resample_order_seg, sep, self.resample_order_z_seg)
+        return out, seg
+
+
+class GenericPreprocessor_linearResampling(_ResizeUnitPreprocessor):
+    """preprocessing.py:402-407: order 1 for the data and for the labels, order 0 along a separately resampled axis."""
+
+    def __init__(self, normalization_scheme_per_modality, use_nonzero_mask, transpose_forward, intensityproperties=None):
+        super().__init__(normalization_scheme_per_modality, use_nonzero_mask, transpose_forward, intensityproperties)
+        self.resample_order_data = 1
+        self.resample_order_seg = 1
+
+
+class Preprocessor3DDifferentResampling(_ResizeUnitPreprocessor):
+    """preprocessing.py:410-491 (the preprocessor of `ExperimentPlanner3D_v23`): order 3 for the data and order 1 for the labels,
+    and along a separately resampled axis order 3 for the data and order 1 for the labels where the default takes order 0."""
+    resample_order_z_data = 3
+    resample_order_z_seg = 1
+
+
+PREPROCESSORS = ("GenericPreprocessor", "GenericPreprocessor_linearResampling", "Preprocessor3DDifferentResampling")

@@ -370,11 +370,12 @@ class nnUNetTrainer(object):
         """Read the case on the host; crop to the non-zero region, resample to the plan's spacing and normalise on the device.  Returns
         (data [C, X, Y, Z] float32, seg, properties) like the reference (numpy; `return_device=True` keeps the volume in HBM)."""
         name = self.plans.get('preprocessor_name') or "GenericPreprocessor"
-        if name != "GenericPreprocessor":
-            raise NotImplementedError("preprocessor %s is not on this path (3D GenericPreprocessor only)" % name)
-        from ...preprocessing.preprocessing import GenericPreprocessor
+        from ...preprocessing import preprocessing
+        if name not in preprocessing.PREPROCESSORS:
+            raise NotImplementedError("preprocessor %s is not on this path (3D only: %s)" % (name, ", ".join(preprocessing.PREPROCESSORS)))
         print("using preprocessor", name)
-        pre = GenericPreprocessor(self.normalization_schemes, self.use_mask_for_norm, self.transpose_forward, self.intensity_properties)
+        pre = getattr(preprocessing, name)(self.normalization_schemes, self.use_mask_for_norm, self.transpose_forward,
+                                           self.intensity_properties)
         return pre.preprocess_test_case(input_files, self.plans['plans_per_stage'][self.stage]['current_spacing'],
                                         return_device=return_device)
 
