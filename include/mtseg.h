@@ -806,7 +806,16 @@ int mt_intensity_apply(float* x, int NC, long V, const mt_intensity_op_t* record
  *   +0.0, NaNs by bit pattern); among the non-negative doubles the entry point was first specified for it selects exactly the element
  *   the plain bit pattern selects.  ws: mt_select_kth_workspace(nranks) bytes of device scratch, 8-byte aligned: ask every time, the
  *   size is not that of earlier builds.  n < 1, a rank outside 0..n-1 or nranks outside 1..8 is MT_EINVAL, too small a workspace
- *   MT_EWORKSPACE, both before any launch. */
+ *   MT_EWORKSPACE, both before any launch.
+ * mt_sd_count_within (an addition to ABI 4): counts[s * T + t] (device int64[2][T], 8-byte aligned) = the number of distances
+ *   <= tols[t] in segment s of the array mt_surface_distances wrote: segment 0 = sds[0, n_tr), segment 1 = sds[n_tr, n_tr + n_rt).
+ *   The normalized surface Dice of evaluation/surface_dice.py:43-56 is host arithmetic on these integers.  tols: HOST array of T
+ *   (1..8) doubles, passed to the kernel by value; the comparison is fp64, so a distance equal to the tolerance is within it; +inf
+ *   counts everything (a NaN distance is within nothing).  The call zeroes `counts` on the stream before the launch: the caller need
+ *   not.  One pass, 8 bytes read per distance; 16-byte loads where the address allows (sds needs 8-byte alignment only and
+ *   n_tr may be odd).  One 64-bit integer atomic per workgroup, segment and tolerance, nothing else: identical from run to run.  T outside 1..8, a negative segment length, n_tr + n_rt < 1,
+ *   a NaN or negative tolerance, a null or misaligned pointer is MT_EINVAL before any launch. */
+int mt_sd_count_within(const double* sds, long n_tr, long n_rt, const double* tols /* host */, int T, int64_t* counts, mt_stream_t stream);
 int mt_seg_joint_hist(const uint8_t* test, const uint8_t* ref, long V, const uint8_t* remap, int C, int64_t* hist, mt_stream_t stream);
 size_t mt_surface_distances_workspace(int D, int H, int W, long capacity);
 int mt_surface_distances(const uint8_t* test, const uint8_t* ref, int D, int H, int W, const uint8_t* member, const double* spacing,

@@ -190,6 +190,7 @@ SIGNATURES = {
     'mt_surface_distances': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _l, _vp, _vp, _sz, _vp]),
     'mt_select_kth_workspace': (_sz, [_i]),
     'mt_select_kth': (_i, [_vp, _l, _vp, _i, _vp, _vp, _sz, _vp]),
+    'mt_sd_count_within': (_i, [_vp, _l, _l, _vp, _i, _vp, _vp]),
     'mt_fg_sample_workspace': (_sz, [_l]),
     'mt_fg_sample_count': (_i, [_vp, _l, _vp, _vp, _sz, _vp]),
     'mt_fg_sample_gather': (_i, [_vp, _i, _l, _vp, _l, _vp, _sz, _vp, _l, _vp, _vp]),

@@ -13,6 +13,7 @@
 //                          each row's candidate from g1, until no unvisited row can be nearer; the distance is
 //                          sqrt((dz sz)^2 + (dy sy)^2 + (dx sx)^2) in fp64 of the integer offsets to the site found;
 //     sd_reduce_kernel x2  count, maximum and sum per direction: fixed 4096-element chunks, fixed tree, no atomics.
+// (mt_sd_count_within, which counts those distances against tolerances, is surface_dice.hip.)
 // Every floating-point result is a function of the inputs alone (integer atomics only): two runs are bit-identical.
 #include "stream_common.h"
 

@@ -7,9 +7,10 @@ With a HIP device the confusion counts of ALL labels of a case come from one joi
 (`mt_seg_joint_hist`); without one, or for volumes that are not integer labels in 0..255, the host loop below counts them.  Both
 feed `metrics_from_counts`, so the default metrics are the same numbers bit for bit.  The advanced metrics (medpy's hd, hd95,
 asd, assd: borders by erosion, exact Euclidean distance transform, `mt_surface_distances` / `mt_select_kth`) exist on the device
-only: without one they raise.
+only: without one they raise.  So does "Normalized Surface Dice" at `nsd_threshold` mm (reference evaluation/surface_dice.py): the
+same distances counted against the tolerance where they lie (`mt_sd_count_within`), two integers per label entry read back.
 
-Run: python -m multitalent_amd.evaluation.evaluator -ref GT_FOLDER -pred PRED_FOLDER -l 1 2 3 [--advanced]"""
+Run: python -m multitalent_amd.evaluation.evaluator -ref GT_FOLDER -pred PRED_FOLDER -l 1 2 3 [--advanced] [--nsd TOL_MM]"""
 import hashlib
 import json
 from collections import OrderedDict
@@ -26,6 +27,7 @@ DEFAULT_METRICS = ["False Positive Rate", "Dice", "Jaccard", "Precision", "Recal
 
 ADVANCED_METRICS = ["Hausdorff Distance", "Hausdorff Distance 95", "Avg. Surface Distance", "Avg. Symmetric Surface Distance"]
 DEFAULT_ADVANCED_METRICS = ["Hausdorff Distance 95"]          # Evaluator.default_advanced_metrics (evaluator.py:53-58)
+NSD_METRIC = "Normalized Surface Dice"                        # accepted in `advanced_metrics` beside ADVANCED_METRICS, with nsd_threshold
 
 
 def metrics_from_counts(tp, fp, fn, tn):
@@ -63,6 +65,36 @@ def confusion_metrics(test, reference):
     fn = int((~test & reference).sum())
     tn = int(test.size) - tp - fp - fn
     return metrics_from_counts(tp, fp, fn, tn)
+
+
+def nsd_from_counts(c_tr, n_tr, c_rt, n_rt):
+    """surface_dice.py:46-55 on integers: n_tr / n_rt border voxels of test / reference, c_tr / c_rt of them within the tolerance
+    of the other border.  Python's float arithmetic on ints below 2^53 is numpy's float64 arithmetic: the same bits."""
+    c_tr, n_tr, c_rt, n_rt = int(c_tr), int(n_tr), int(c_rt), int(n_rt)
+    tp_a = c_tr / n_tr
+    tp_b = c_rt / n_rt
+    fp = (n_tr - c_tr) / n_tr
+    fn = (n_rt - c_rt) / n_rt
+    return (tp_a + tp_b) / (tp_a + tp_b + fp + fn + 1e-8)
+
+
+def _nsd_tolerances(labels, nsd_threshold):
+    """{str(label): tolerance in mm} from a number for all entries or a dict {str(label): number}; an entry without one, or a
+    tolerance that is not a number >= 0, is a ValueError."""
+    out = OrderedDict()
+    for l in labels:
+        v = nsd_threshold.get(str(l)) if isinstance(nsd_threshold, dict) else nsd_threshold
+        if v is None:
+            raise ValueError("%r needs nsd_threshold: a tolerance in mm, or a dict {str(label): mm} with an entry for label %s"
+                             % (NSD_METRIC, l))
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("nsd_threshold for label %s must be a number, got %r" % (l, v))
+        if not v >= 0:                                          # False for NaN
+            raise ValueError("nsd_threshold for label %s must be >= 0, got %r" % (l, v))
+        out[str(l)] = v
+    return out
 
 
 def _no_device():
@@ -149,8 +181,9 @@ def _percentile_linear(lo_value, hi_value, gamma):
     return hi_value - d * (1 - gamma) if gamma >= 0.5 else lo_value + d * gamma
 
 
-def _surface_metrics(t, r, members, counts, names, voxel_spacing, connectivity):
-    """The advanced metrics of one label entry (metrics.py:314-383 over medpy's hd / hd95 / asd / assd)."""
+def _surface_metrics(t, r, members, counts, names, voxel_spacing, connectivity, nsd_tolerance=None):
+    """The advanced metrics of one label entry (metrics.py:314-383 over medpy's hd / hd95 / asd / assd; NSD_METRIC at
+    nsd_tolerance: surface_dice.py:43-56 on the same distances, one more launch and 16 bytes read back)."""
     tp, fp, fn, tn = counts
     nan = float("NaN")
     if (tp + fp) == 0 or (tn + fn) == 0 or (tp + fn) == 0 or (tn + fp) == 0:       # test / reference empty or full
@@ -182,6 +215,9 @@ def _surface_metrics(t, r, members, counts, names, voxel_spacing, connectivity):
                 res[k] = sum_tr / n_tr
             elif k == "Avg. Symmetric Surface Distance":
                 res[k] = float(np.mean((sum_tr / n_tr, sum_rt / n_rt)))
+            elif k == NSD_METRIC:
+                (c_tr,), (c_rt,) = ops.sd_count_within(sds, n_tr, n_rt, [nsd_tolerance]).cpu().tolist()
+                res[k] = nsd_from_counts(c_tr, n_tr, c_rt, n_rt)
     return res
 
 
@@ -206,21 +242,27 @@ def _load(x):
     return np.asarray(x), None, None
 
 
-def evaluate_case(test_file, ref_file, labels, advanced=False, advanced_metrics=None, voxel_spacing=None, connectivity=1):
+def evaluate_case(test_file, ref_file, labels, advanced=False, advanced_metrics=None, voxel_spacing=None, connectivity=1,
+                  nsd_threshold=None):
     """labels: iterable of ints or tuples of ints (a tuple = the union of its members, evaluator.py:140-160).  test_file /
     ref_file: file names, numpy arrays or HIP device tensors.  advanced=True appends `advanced_metrics` (default
     DEFAULT_ADVANCED_METRICS; any of ADVANCED_METRICS) with `voxel_spacing` (z, y, x) - default: the test file's spacing, unit
-    spacing for arrays (NiftiEvaluator.evaluate, evaluator.py:297-303) - and `connectivity` 1..3 of the erosion structure."""
+    spacing for arrays (NiftiEvaluator.evaluate, evaluator.py:297-303) - and `connectivity` 1..3 of the erosion structure.
+    `advanced_metrics` may also name NSD_METRIC; then `nsd_threshold` is its tolerance in mm: one number, or a dict
+    {str(label): number} with an entry for every label."""
+    labels = list(labels)
+    nsd = {}
+    if advanced and advanced_metrics is not None and NSD_METRIC in advanced_metrics:
+        nsd = _nsd_tolerances(labels, nsd_threshold)            # before a file is read or the device is asked
     test, test_name, test_spacing = _load(test_file)
     ref, ref_name, _ = _load(ref_file)
     if tuple(test.shape) != tuple(ref.shape):
         raise ValueError("Shape mismatch: %s and %s" % (tuple(test.shape), tuple(ref.shape)))
-    labels = list(labels)
     names = []
     if advanced:
         names = list(DEFAULT_ADVANCED_METRICS if advanced_metrics is None else advanced_metrics)
         for k in names:
-            if k not in ADVANCED_METRICS:
+            if k not in ADVANCED_METRICS and k != NSD_METRIC:
                 raise ValueError("unknown advanced metric %r (one of %s)" % (k, ADVANCED_METRICS))
         if connectivity not in (1, 2, 3):
             raise ValueError("connectivity %r (1, 2 or 3)" % (connectivity,))
@@ -241,7 +283,7 @@ def evaluate_case(test_file, ref_file, labels, advanced=False, advanced_metrics=
             res[str(l)] = metrics_from_counts(*counts[str(l)])
             if names:
                 res[str(l)].update(_surface_metrics(pair[0], pair[1], _members(l), counts[str(l)], names, voxel_spacing,
-                                                    connectivity))
+                                                    connectivity, nsd.get(str(l))))
     else:
         if names:
             raise ValueError("advanced metrics need integer label volumes with values in 0..255")
@@ -261,7 +303,7 @@ def evaluate_case(test_file, ref_file, labels, advanced=False, advanced_metrics=
 
 def aggregate_scores(test_ref_pairs, labels=None, nanmean=True, json_output_file=None, json_name="", json_description="",
                      json_author="Fabian", json_task="", num_threads=2, evaluator=None, advanced=False, advanced_metrics=None,
-                     voxel_spacing=None, connectivity=1):
+                     voxel_spacing=None, connectivity=1, nsd_threshold=None):
     """evaluator.py:321-400.  `evaluator` and `num_threads` are accepted for the reference's callers and not used: the cases
     run one after another on the device.  Any other unknown keyword is a TypeError."""
     if labels is None:
@@ -269,7 +311,7 @@ def aggregate_scores(test_ref_pairs, labels=None, nanmean=True, json_output_file
     scores = OrderedDict(all=[], mean=OrderedDict())
     for test, ref in test_ref_pairs:
         scores["all"].append(evaluate_case(test, ref, labels, advanced=advanced, advanced_metrics=advanced_metrics,
-                                           voxel_spacing=voxel_spacing, connectivity=connectivity))
+                                           voxel_spacing=voxel_spacing, connectivity=connectivity, nsd_threshold=nsd_threshold))
     for res in scores["all"]:
         for label, sd in res.items():
             if label in ("test", "reference"):
@@ -310,7 +352,7 @@ def evaluate_folder(folder_with_gts, folder_with_predictions, labels, **metric_k
 
 
 def main(argv=None):
-    """The reference's nnunet_evaluate_folder (evaluator.py:464-483), plus --advanced."""
+    """The reference's nnunet_evaluate_folder (evaluator.py:464-483), plus --advanced and --nsd."""
     import argparse
     parser = argparse.ArgumentParser("Evaluates the segmentations located in the folder pred. Output of this script is a json "
                                      "file. At the very bottom of the json file is going to be a 'mean' entry with averages "
@@ -322,8 +364,14 @@ def main(argv=None):
     parser.add_argument('--advanced', action='store_true', help="Also the surface-distance metrics (HIP device only).")
     parser.add_argument('--advanced_metrics', nargs='+', default=None, help="Any of: %s" % ", ".join(repr(i) for i in ADVANCED_METRICS))
     parser.add_argument('--connectivity', type=int, default=1)
+    parser.add_argument('--nsd', type=float, default=None, metavar='TOL', help="Also %r at this tolerance in mm (HIP device only)."
+                                                                               % NSD_METRIC)
     args = parser.parse_args(argv)
     kw = dict(advanced=True, advanced_metrics=args.advanced_metrics, connectivity=args.connectivity) if args.advanced else {}
+    if args.nsd is not None:
+        names = list(kw['advanced_metrics'] or DEFAULT_ADVANCED_METRICS) if kw else []
+        kw = dict(advanced=True, advanced_metrics=names + [NSD_METRIC] * (NSD_METRIC not in names), connectivity=args.connectivity,
+                  nsd_threshold=args.nsd)
     return evaluate_folder(args.ref, args.pred, args.l, **kw)
 
 

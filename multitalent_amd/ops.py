@@ -1253,6 +1253,35 @@ def select_kth(x, ranks, out=None, ws=None):
     return _select_kth(x, ranks, out, ws, torch.float64, 'select_kth')
 
 
+SD_COUNT_MAX_TOLERANCES = 8
+
+
+def sd_count_within(sds, n_tr, n_rt, tolerances, out=None):
+    """sds: the 1-D contiguous fp64 device tensor surface_distances wrote (8-byte aligned; n_tr + n_rt <= len(sds)); tolerances: 1..8
+    host numbers >= 0 (+inf allowed).  -> int64 device tensor [2, T]: how many of sds[:n_tr] (row 0) and of sds[n_tr:n_tr + n_rt]
+    (row 1) are <= each tolerance, compared in fp64 (see mt_sd_count_within).  `out` is zeroed by the call.  Nothing is synchronised."""
+    tol = np.ascontiguousarray(np.asarray(tolerances, dtype=np.float64).reshape(-1))
+    n_tr, n_rt = int(n_tr), int(n_rt)
+    if not 1 <= tol.size <= SD_COUNT_MAX_TOLERANCES:
+        raise ValueError("sd_count_within: %d tolerances (1..%d)" % (tol.size, SD_COUNT_MAX_TOLERANCES))
+    if not np.all(tol >= 0):                                    # False for NaN
+        raise ValueError("sd_count_within: tolerances must be numbers >= 0, got %s" % (tol.tolist(),))
+    if n_tr < 0 or n_rt < 0 or n_tr + n_rt < 1:
+        raise ValueError("sd_count_within: bad segment lengths %d, %d" % (n_tr, n_rt))
+    if sds.dim() != 1 or n_tr + n_rt > sds.numel():
+        raise ValueError("sd_count_within: %d + %d distances do not fit a tensor of shape %s" % (n_tr, n_rt, tuple(sds.shape)))
+    _require_device(_EVAL, sds)
+    assert sds.dtype == torch.float64 and sds.is_contiguous()
+    T = int(tol.size)
+    if out is None:
+        out = torch.empty((2, T), dtype=torch.int64, device=sds.device)
+    _require_device(_EVAL, out)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == 2 * T
+    _lib.check(_lib.load().mt_sd_count_within(_ptr(sds), n_tr, n_rt, tol.ctypes.data_as(C.c_void_p), T, _ptr(out), _stream()),
+               'sd_count_within')
+    return out.view(2, T)
+
+
 FG_MAX_CHANNELS = 16
 LABEL_PRESENCE_MIN, LABEL_PRESENCE_MAX = -1, 1022
 
