@@ -595,6 +595,7 @@ class Engine:
         self.flat = None
         self.flat_grad = None
         self._views = {}
+        self._params = []
         self.params_version = 0
         self.wstreams = []                  # side streams of the backward-weight launches (Engine.weight_stream)
         self._wnext = 0
@@ -623,6 +624,25 @@ class Engine:
         self._fuse_norm_bwd = None          # None: the default below; tests set 0 ... 3
         self._one_stream_at_init = self.bwdw_streams == 0       # (the default follows the stream setting the engine was built with)
         self.producer, self.pending = {}, {}
+
+    # what belongs to ONE engine on ONE device and is rebuilt by attach() / _plan() / _pack() on the first forward
+    _DEVICE_STATE = dict(_buffers=dict, _ws=None, _ws_side=dict, wstreams=list, _late_pack=None, _mid_pack=None, _pack_programs=dict,
+                         _io_cache=dict, _fp32_copies=dict, flat=None, flat_grad=None, _views=dict, _params=list, dummy=None,
+                         producer=dict, pending=dict, _planned=None, _packed_version=None, grad_ready_hook=None)
+
+    def __deepcopy__(self, memo):
+        """copy.deepcopy(network): the copy gets an engine of its own over the copied modules, without the device state (HIP streams
+        and events cannot be copied, and buffers, views and packing programs point into the original's memory): its first forward
+        re-homes the copied parameters and plans and packs afresh."""
+        import copy
+        new = type(self).__new__(type(self))
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k not in self._DEVICE_STATE and k != '_op_ranges':
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        for k, v in self._DEVICE_STATE.items():
+            new.__dict__[k] = v() if v is not None else None
+        return new
 
     @property
     def fuse_norm_bwd(self):
@@ -783,6 +803,7 @@ class Engine:
             flat[o:o + p.numel()].copy_(p.data.reshape(-1))
             p.data = flat[o:o + p.numel()].view(p.shape)
         self.flat = flat
+        self._params = params
         self.flat_grad = torch.zeros_like(flat)
         self._views = {id(p): (o, self.flat_grad[o:o + p.numel()].view(p.shape)) for p, o in zip(params, offs)}
         self._op_ranges = []
@@ -836,12 +857,16 @@ class Engine:
         self._fp32_copies.clear()
 
     def _pack(self, need_grad):
-        ver = (self.params_version, self.flat._version, need_grad)
+        # in-place updates through the parameters (a stock optimizer's step, load_state_dict, p.add_() under no_grad) move the
+        # PARAMETERS' version counters, not the flat buffer's: attach() re-homed each as `p.data = view`, which gives it a counter of its
+        # own.  Counters only grow, so their sum changes whenever one does (host integers: no device sync).  Writes that no counter sees
+        # — through `p.data`, or by a kernel on raw pointers as in FusedTrainStep — still need mark_params_dirty()
+        ver = (self.params_version, self.flat._version, sum(p._version for p in self._params), need_grad)
         if self._packed_version == ver:
             return
         # the program only holds POINTERS (weights inside the flat buffer, packed destinations): it stays valid until attach(),
         # _plan() or set_precision() clear it — parameter VALUES changing (every optimizer step) just re-runs it
-        key = need_grad
+        key = (need_grad, self.bwdw_streams > 0)         # (the split below depends on the stream setting, which may change between steps)
         prog = self._pack_programs.get(key)
         if key not in self._pack_programs:   # record the ops' packing calls once; afterwards every step is one batched launch
             def record(bwd):
@@ -1010,12 +1035,17 @@ class _UNetFunction(torch.autograd.Function):
     def forward(ctx, eng, all_heads, x, *params):
         ctx.eng, ctx.all_heads = eng, all_heads
         outs = eng.forward(x, need_grad=True, all_heads=all_heads)
+        ctx.iter = eng._iter
         ctx.nparams = len(params)
         return tuple(o.permute(0, 4, 1, 2, 3) for o in outs)
 
     @staticmethod
     def backward(ctx, *gouts):
         eng = ctx.eng
+        if eng._iter != ctx.iter:
+            # the activations backward reads (and the logits the loss was taken on) live in buffers that every forward overwrites
+            raise RuntimeError("multitalent_amd: backward through a forward pass whose buffers a later forward of the same network has "
+                               "overwritten (forward %d, the engine is at %d): run backward before the next forward" % (ctx.iter, eng._iter))
         gl = []
         for g in gouts:
             gl.append(None if g is None else g.permute(0, 2, 3, 4, 1).contiguous())

@@ -18,36 +18,7 @@ def relerr(a, b):
     return float((a - b).abs().max() / (b.abs().max() + 1e-12))
 
 
-def build_plain(nc, base=10, pools=((2, 2, 2), (2, 2, 2), (1, 2, 2)), kernels=None, in_ch=1):
-    from multitalent_amd.network_architecture.generic_UNet import Generic_UNet
-    from multitalent_amd.network_architecture.initialization import InitWeights_He
-    pools = [list(p) for p in pools]
-    kernels = [[3, 3, 3]] * (len(pools) + 1) if kernels is None else kernels
-    torch.manual_seed(0)
-    net = Generic_UNet(in_ch, base, nc, len(pools), 2, 2, nn.Conv3d, nn.InstanceNorm3d, {'eps': 1e-5, 'affine': True},
-                       nn.Dropout3d, {'p': 0, 'inplace': True}, nn.LeakyReLU, {'negative_slope': 1e-2, 'inplace': True},
-                       True, False, lambda x: x, InitWeights_He(1e-2), pools, kernels, False, True, True)
-    # make norm affine params and biases non-trivial
-    g = torch.Generator().manual_seed(1)
-    for n, p in net.named_parameters():
-        if 'instnorm.weight' in n:
-            p.data = 0.5 + torch.rand(p.shape, generator=g)
-        elif n.endswith('bias'):
-            p.data = 0.2 * torch.randn(p.shape, generator=g)
-    return net, pools, kernels
-
-
-def make_targets(shape, scales, nlabels, B, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    full = torch.randint(0, nlabels, (B, 1) + tuple(shape), generator=g).float()
-    # blocky labels: nearest-neighbour upsample of a coarse grid
-    coarse = torch.randint(0, nlabels, (B, 1) + tuple(max(s // 4, 1) for s in shape), generator=g).float()
-    full = torch.nn.functional.interpolate(coarse, size=tuple(shape), mode='nearest')
-    out = []
-    for sc in scales:
-        size = tuple(int(round(s * f)) for s, f in zip(shape, sc))
-        out.append(torch.nn.functional.interpolate(full, size=size, mode='nearest'))
-    return out
+from engine_cases import build_plain, build_resenc, make_targets  # noqa: E402  (shared with tests/test_engine_*_gpu.py)
 
 
 def test_plain_unet_softmax_fwd_bwd(dev):
@@ -123,23 +94,11 @@ def test_plain_unet_multitalent_loss(dev):
 
 
 def test_resenc_unet_fwd_bwd(dev):
-    from multitalent_amd.network_architecture.generic_modular_residual_UNet import FabiansUNet, get_default_network_config
-    from multitalent_amd.network_architecture.initialization import InitWeights_He
     from multitalent_amd.training.loss_functions.fused_losses import MultiTalentLoss
     from multitalent_amd.dataset_conversion.Task100_MultiTalent import (MultiTalent_regions, MultiTalent_region_output_idx_mapping,
                                                                         MultiTalent_valid_regions)
-    pools = [[1, 1, 1], [1, 2, 2], [2, 2, 2], [2, 2, 2]]
-    kernels = [[1, 3, 3], [3, 3, 3], [3, 3, 3], [3, 3, 3]]
-    blocks = [1, 2, 2, 2]
-    torch.manual_seed(0)
-    net = FabiansUNet(1, 8, blocks, 2, pools, kernels, get_default_network_config(3, None, norm_type="in"), 47, [1, 1, 1],
-                      True, False, 24, InitWeights_He(1e-2))
     g = torch.Generator().manual_seed(1)
-    for n, p in net.named_parameters():
-        if 'norm' in n and n.endswith('weight') and p.dim() == 1:
-            p.data = 0.5 + torch.rand(p.shape, generator=g)
-        elif n.endswith('bias'):
-            p.data = 0.2 * torch.randn(p.shape, generator=g)
+    net, pools, kernels, blocks = build_resenc(47, generator=g)      # (the input below continues g's stream, as it always did)
     sd = {k: v.detach().clone().requires_grad_(True) for k, v in net.state_dict().items() if '.all.' not in k}
     B, shape = 2, (8, 32, 32)
     x = torch.randn((B, 1) + shape, generator=g)
